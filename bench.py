@@ -1,8 +1,15 @@
 #!/usr/bin/env python
 """bench.py - env-steps/s of the MADRQN hetero-GNN hot path on MI355X (BASELINE.json metric), one JSON line.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line (headline `value` / `ms_per_step`, the `roofline` of the graded
+kernel from the HIP events of the timed region, the run's own diagnostics).  Everything that takes runs of its own - the extra
+instrumented cycle (`roofline_secondary`, `kernel_ms_per_launch`), the vendor-GEMM calibration, the graphed-cycle, fp32-MFMA,
+D-env, replay-ratio and simulator-inclusive legs and the CPU baseline - runs only with ``--full``.  ``--dump-outputs DIR`` writes
+what the last timed step handed its caller (loss, Q-values, the rollout's last actions and recurrent state, the parameters after
+the update) as DIR/<name>.npy in float32; inputs and initial weights are seeded, so two builds can be compared output for output.
 
 Workload (config.workload, SURVEY 8d "C3"): 8 UBS x 80 GT env graphs, exp3 model (H=256, 4 heads, TarMAC msg 64 /
 key 16, 9 actions), B = 4096 env graphs per GPU, degree distribution D-dense (every agent sees all 80 GTs, 7 neighbours,
@@ -16,7 +23,7 @@ Such a cycle advances B*T environment steps, so  value = N * B * T * K / elapsed
 B per GPU fixed).  The simulator itself is out of scope: graphs are synthetic and resident in HBM
 before the timed region, exactly as the reference's sampled batch is when ``update`` starts its forward passes.
 
-Extra objects: ``roofline`` for the dominant message-passing kernel (K1 forward, BOTH relations in one fused launch),
+Extra objects (``--full`` for all but ``roofline``): ``roofline`` for the dominant message-passing kernel (K1 forward, BOTH relations in one fused launch),
 measured live with HIP events around every one of its launches inside the timed region - reported against the roof that binds at the
 launch mix's arithmetic intensity (fp32 MFMA peak for the dense workload, HBM for env-realistic degrees), with both
 fractions kept side by side (``hbm``, ``mfma_fp32``); ``cpu_baseline`` = the CPU oracle
@@ -716,6 +723,28 @@ def metric_name(a):
     return f"env-steps/sec (MADRQN, {a.n} UBS x {a.M} GT)"
 
 
+DUMP_CAP = 1 << 20      # elements per dumped array (4 MB of float32); larger outputs are written as a fixed, seeded sample
+
+
+def dump_outputs(path, out, last, learner):
+    """--dump-outputs: what the LAST timed step handed its caller, as DIR/<name>.npy (float32): `loss` and `qvals` (the update's
+    return), `actions` and `hidden` (the last rollout step's return), `policy_params` / `target_params` (every parameter after the
+    update's AdamW + polyak, flattened in parameters() order).  An array of more than DUMP_CAP elements is written as the
+    flattened values at DUMP_CAP sorted positions drawn without replacement by a generator seeded with 0, the same positions in
+    every run of the same sizes.  Six arrays of at most 4 MB each: 24 MB at most."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    flat = lambda m: th.cat([p.detach().reshape(-1) for p in m.parameters()])  # noqa: E731
+    arrays = {"loss": out["LossQ"], "qvals": out["QVals"], "actions": last["acts"], "hidden": last["h"],
+              "policy_params": flat(learner.policy_net), "target_params": flat(learner.target_net)}
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() > DUMP_CAP:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_CAP, replace=False))
+            t = t.reshape(-1)[th.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -743,7 +772,14 @@ def main():
                          "rows per GPU, single process.  `value` is always the eager cycle" % GRAPHED_CYCLE_ROWS)
     ap.add_argument("--no-fp32-leg", action="store_true",
                     help="skip the second timing with the bf16x3 kernels off (fp32-MFMA GRU cell, vendor fp32 GEMMs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the instrumented cycle, the MFMA calibration and the extra legs "
+                         "(graphed cycle, fp32 MFMA, D-env, replay ratio, end-to-end, CPU baseline; each --no-* flag still skips its own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "RANK" not in os.environ:
         # plain `python3 bench.py --gpus N`: this process is the launcher, not a rank
@@ -800,7 +836,7 @@ def main():
         learner.grads.force_collective = True    # world size 1: still push the flat gradient buffer through RCCL
     batch = make_sequence(a.B, a.n, a.M, a.T, a.dist, device, seed=1234 + rank, distinct=a.distinct)
 
-    def step():
+    def step(keep=None):
         # Every cycle sees NEWLY BUILT graphs: .fresh() shares the arrays but drops every derived index (K1 hand-out
         # order, talk-CSC transpose), so building them is inside the timed region - as with fresh observations from a
         # simulator or a new replay sample (the reference pays DGL's lazy CSR/CSC materialisation the same way).
@@ -808,8 +844,11 @@ def main():
         fb = dict(batch, obs=obs, obs_all=batch["obs_all"].fresh(), obs_all_next=batch["obs_all_next"].fresh())
         h = learner.init_hidden(a.B)
         for t in range(a.T):
-            _, h = learner.act(obs[t].fresh(), h, 0.05)
-        return learner.update(fb)
+            acts, h = learner.act(obs[t].fresh(), h, 0.05)
+        out = learner.update(fb)
+        if keep is not None:      # the last rollout step's return, for --dump-outputs (alive until here anyway)
+            keep.update(acts=acts, h=h)
+        return out
 
     def barrier():
         if use_dist:
@@ -820,12 +859,12 @@ def main():
     # already sits at a fixed device address), is reported as an EXTRA leg (`graphed_cycle_leg` / `value_graphed`) behind the timed
     # region.  The headline `value` is always the eager cycle: a replay bakes the stored batch's topology into the graph, which a
     # loop fed fresh observations could only reproduce with capacity-sized (static) graphs.
-    want_graphed = not use_dist and (a.graphed_cycle == "on" or (a.graphed_cycle == "auto" and a.B * a.n <= GRAPHED_CYCLE_ROWS))
+    want_graphed = a.full and not use_dist and (a.graphed_cycle == "on" or (a.graphed_cycle == "auto" and a.B * a.n <= GRAPHED_CYCLE_ROWS))
     eager_step = step
 
     # Inside the timed region only the GRADED kernel (K1 forward) carries HIP events: timing every launch costs the launch thread
     # ~15 us per launch and makes the rollout phase host-bound (tools/launch_bound_probe.py: 21 -> 29 ms per 50 act forwards).
-    # The other kernels are timed in ONE extra, fully instrumented cycle after the timed region (`instrumented_cycle`).
+    # The other kernels are timed in ONE extra, fully instrumented cycle after the timed region (`instrumented_cycle`, --full only).
     GRADED = ("gatv2_hetero_fwd",)
     ops.KERNEL_TIMER.reset(enabled=True, only=GRADED)   # warm-up runs instrumented the same way
     # Python's cyclic GC is kept out of the timed region (a gen-2 pass over the autograd objects of a 101-forward
@@ -845,9 +884,9 @@ def main():
     alloc0 = th.cuda.memory_stats(device).get("num_device_alloc", 0)
     with clock:
         t0 = time.perf_counter()
-        marks, enq, allocs_by_step = [], [], []
-        for _ in range(a.steps):
-            out = step()
+        marks, enq, allocs_by_step, last = [], [], [], {}
+        for i in range(a.steps):
+            out = step(last if a.dump_outputs and i == a.steps - 1 else None)
             ev = th.cuda.Event(enable_timing=True)
             ev.record()
             marks.append(ev)
@@ -861,12 +900,18 @@ def main():
     learner.grads.collective_events = None
     clock_info = clock.summary()
     clock_mhz = clock_info["mean_mhz"] if clock_info else None
-    ops.KERNEL_TIMER.reset(enabled=True)              # every span: one more cycle, on every rank (the update holds a collective)
-    t_i = time.perf_counter()
-    eager_step()
-    barrier()
-    instr_s = time.perf_counter() - t_i
-    kfull = ops.KERNEL_TIMER.summary()
+    ck = params_checksum(learner.policy_net)          # the parameters the timed steps left (before any further cycle)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out, last, learner)
+    last.clear()
+    kfull, instr_s = {}, None
+    if a.full:
+        ops.KERNEL_TIMER.reset(enabled=True)          # every span: one more cycle, on every rank (the update holds a collective)
+        t_i = time.perf_counter()
+        eager_step()
+        barrier()
+        instr_s = time.perf_counter() - t_i
+        kfull = ops.KERNEL_TIMER.summary()
     gc.enable()
     ops.KERNEL_TIMER.enabled = False
     el = th.tensor([elapsed], device=device, dtype=th.float64)
@@ -874,7 +919,6 @@ def main():
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el)
     loss = float(out["LossQ"])
-    ck = params_checksum(learner.policy_net)
     if use_dist:   # replicas must stay bit-identical
         lo, hi = ck.clone(), ck.clone()
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
@@ -924,6 +968,7 @@ def main():
                                                # (run.py:55-57,:97: rho = 32) is `value_rho32` below, from the `replay_ratio_leg`
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / a.steps,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "full": a.full,                    # False: the headline only; --full adds the instrumented cycle and the extra legs
             "config": {"workload": f"{label}: {a.n} UBS x {a.M} GT, exp3 MADRQN (GATv2 obs-encoder + TarMAC), "
                                    f"B={a.B} env graphs/GPU, T={a.T}, D-{a.dist}, replay ratio 1: one step = {a.T} "
                                    f"act forwards + 1 update ({2 * a.T + 1} forwards + BPTT backward + AdamW)",
@@ -1017,11 +1062,12 @@ def main():
                     if e.get("bound") == "mfma" and e["peak"] == BF16_PEAK_TFLOPS:
                         e["frac_of_vendor_bf16_gemm_rate"] = e["achieved"] / cal["tflops"]
             res["roofline_secondary"] = sec
-        res["kernel_ms_per_launch"] = {n: round(v["avg_ms"], 4) for n, v in kfull.items()}
-        res["instrumented_cycle"] = {"ms": 1e3 * instr_s,
-                                     "note": "one extra cycle AFTER the timed steps with HIP events around every C-ABI launch: source of "
-                                             "`roofline_secondary` and `kernel_ms_per_launch`.  The timed steps carry events around the "
-                                             "graded kernel (`roofline`) only - timing every launch makes the rollout host-bound"}
+        if a.full:
+            res["kernel_ms_per_launch"] = {n: round(v["avg_ms"], 4) for n, v in kfull.items()}
+            res["instrumented_cycle"] = {"ms": 1e3 * instr_s,
+                                         "note": "one extra cycle AFTER the timed steps with HIP events around every C-ABI launch: source of "
+                                                 "`roofline_secondary` and `kernel_ms_per_launch`.  The timed steps carry events around the "
+                                                 "graded kernel (`roofline`) only - timing every launch makes the rollout host-bound"}
         res["arithmetic"] = ("fp32 in / out / accumulate everywhere.  K3b, K5 and all pointwise kernels: fp32 FMA.  GEMM-shaped products run on the "
                              "16-bit matrix cores at fp32 accuracy, in two exact-split schemes.  f16x2 (round 6; csrc/gru_h2.hip, gemm_h2.hip, "
                              "gemm_tn_h2.hip): every row (column, for the weight gradients) of an operand is scaled by an exact power of two into "
@@ -1037,7 +1083,7 @@ def main():
                              "r02_gemm_x3_probe.txt, r03_gru_probe.txt).  A/B switches: UAVGNN_GRU_H2=0 / UAVGNN_GEMM_H2=0 / "
                              "UAVGNN_GEMM_TN_H2=0 fall back to bf16x3 / the vendor GEMM.  `fp32_mfma_leg` is the same cycle with ALL of them "
                              "switched to fp32 MFMA / vendor fp32 GEMMs (UAVGNN_GRU_X3=0 UAVGNN_GEMM_X3=0 UAVGNN_K1_BF16Z=0).")
-        if world == 1 and not a.no_fp32_leg:
+        if a.full and world == 1 and not a.no_fp32_leg:
             saved_flags = (ops.GRU_X3, ops.GEMM_X3, ops.K1_BF16Z)     # a run started with UAVGNN_*=0 keeps its own setting afterwards
             ops.GRU_X3 = ops.GEMM_X3 = ops.K1_BF16Z = False
             try:
@@ -1058,7 +1104,7 @@ def main():
                                                   "on fp32 MFMA (csrc/gatv2_hetero_f32.hip): no bf16 instruction anywhere"}
             finally:
                 ops.GRU_X3, ops.GEMM_X3, ops.K1_BF16Z = saved_flags
-        if world == 1 and a.dist == "dense" and not a.no_env_leg:
+        if a.full and world == 1 and a.dist == "dense" and not a.no_env_leg:
             # ---- the HBM-bound regime of the graded kernel inside the default run: the same cycle on D-env degrees (94 % of the
             # agents see no GT - a random-policy rollout), a few steps, K1 forward timed live the same way
             env_batch = make_sequence(a.B, a.n, a.M, a.T, "env", device, seed=4321, distinct=a.distinct)
@@ -1102,7 +1148,7 @@ def main():
                     r_env["standalone"] = {"error": repr(e)}
                 res["roofline_env"] = r_env
             del env_batch
-        if world == 1 and not a.no_rho_leg:
+        if a.full and world == 1 and not a.no_rho_leg:
             # the reference's own replay ratio (run.py:55-57,:97: 32 stored sequences per T steps of one environment):
             # T act forwards on B environments + ONE optimizer step over rho chunks of B sequences (gradient accumulation)
             rho = a.rho
@@ -1135,10 +1181,10 @@ def main():
                                        "config": f"{a.T} act forwards on B environments + one optimizer step over {rho} chunks "
                                                  f"of B sequences (the same synthetic chunk {rho} times; gradients accumulated "
                                                  "in the flat buffer, ONE clip + AdamW + polyak)"}
-        if world == 1 and not a.no_end_to_end:
+        if a.full and world == 1 and not a.no_end_to_end:
             res["end_to_end"] = end_to_end(learner, a, device, "random")
             res["end_to_end_hotspot"] = end_to_end(learner, a, device, "hotspot")
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(a.n, a.M, a.dist)
         emit(json.dumps(res))
     if use_dist:

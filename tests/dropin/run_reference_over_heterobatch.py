@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""BUILD-CONTAINER-ONLY proof of INTEGRATION.md's drop-in claim (needs /root/reference; never runs on the GPU box).
+"""Proof of INTEGRATION.md's drop-in claim, run by hand against a checkout of the reference project (not part of the test suite:
+the repository does not hold the reference's sources).  Usage: python tests/dropin/run_reference_over_heterobatch.py REFERENCE_TREE
 
 The reference's OWN, UNCHANGED modules - envs/mubs_cov (simulator), algos/madrqn/utils/env_wrappers.py
 (GraphObservation.build_obs_graph / local_observation, MultiUbsCoverageWrapper.observation / build_comm_graph),
@@ -26,7 +27,9 @@ import torch as th
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = "/root/reference"
+if len(sys.argv) != 2 or not os.path.isdir(os.path.join(sys.argv[1], "algos")):
+    sys.exit("usage: run_reference_over_heterobatch.py REFERENCE_TREE (the directory that holds algos/ and envs/)")
+REF = os.path.abspath(sys.argv[1])
 sys.path[:0] = [os.path.join(ROOT, "oracle", "gym_standin"), REF, ROOT]
 
 import uav_bs_ctrl_amd.graph as G  # noqa: E402

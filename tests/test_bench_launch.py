@@ -14,6 +14,7 @@ import os
 import socket
 import subprocess
 import sys
+import types
 
 import pytest
 
@@ -93,3 +94,28 @@ def test_rccl_transport_summary_reads_an_nccl_debug_log(tmp_path):
     assert s["channel_transports"] == {"P2P/IPC": 2, "P2P/direct pointer": 1}
     assert s["log_lines"] == 7 and any("Connected all rings" in ln for ln in s["lines"])
     assert bench.rccl_transport_summary(str(tmp_path / "missing.log")) is None
+
+
+def test_dump_outputs_writes_float32_arrays_and_samples_large_ones_reproducibly(tmp_path):
+    """`--dump-outputs DIR`: one float32 .npy per output of the last timed step; an output above DUMP_CAP elements is written as the
+    same seeded sample in every run, so two builds compare position for position."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch as th
+
+    import bench
+    big = th.arange(bench.DUMP_CAP + 1000, dtype=th.float64).reshape(-1, 8)
+    learner = types.SimpleNamespace(policy_net=th.nn.Linear(3, 2), target_net=th.nn.Linear(3, 2))
+    out = dict(LossQ=th.tensor(0.25), QVals=big)
+    last = dict(acts=th.tensor([3, 1, 4], dtype=th.int64), h=th.ones(3, 5))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out, last, learner)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["actions.npy", "hidden.npy", "loss.npy", "policy_params.npy", "qvals.npy", "target_params.npy"]
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float32 and np.array_equal(x, y), n
+    q = np.load(tmp_path / "a" / "qvals.npy")
+    assert q.shape == (bench.DUMP_CAP,) and np.all(np.diff(q) > 0) and set(q.tolist()) <= set(range(big.numel()))
+    assert np.load(tmp_path / "a" / "actions.npy").tolist() == [3.0, 1.0, 4.0]
+    assert np.load(tmp_path / "a" / "policy_params.npy").size == 8 and float(np.load(tmp_path / "a" / "loss.npy")) == 0.25

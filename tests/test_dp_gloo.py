@@ -65,10 +65,14 @@ def _concat(b0, b1):
 
 def _learner():
     import uav_bs_ctrl_amd.learner as LM
-    LM.agent_REGISTRY = {"gnn": OracleAgent}
-    th.manual_seed(123 + (dist.get_rank() if dist.is_initialized() else 0))   # different init per rank on purpose
-    env_info = dict(obs_shape=dict(agent=2, ubs=2, gt=4), n_actions=5, n_agents=N_AG, episode_limit=T)
-    return LM.MultiAgentQLearner(env_info, _args())
+    saved = LM.agent_REGISTRY      # the CPU stand-in only for the learner built here: a test run later in the same process (the
+    LM.agent_REGISTRY = {"gnn": OracleAgent}      # HIP learners of the -m gpu tests) must get the real agent back
+    try:
+        th.manual_seed(123 + (dist.get_rank() if dist.is_initialized() else 0))   # different init per rank on purpose
+        env_info = dict(obs_shape=dict(agent=2, ubs=2, gt=4), n_actions=5, n_agents=N_AG, episode_limit=T)
+        return LM.MultiAgentQLearner(env_info, _args())
+    finally:
+        LM.agent_REGISTRY = saved
 
 
 def _worker(rank, world, port, q):
@@ -143,7 +147,17 @@ def test_dp2_gradient_equals_single_process_on_concatenated_batch():
     assert float((res["grad"] - ref).abs().max()) <= 1e-5 * scale + 1e-9, "DP-2 mean gradient != big-batch gradient"
     L.update(both)
     after = th.cat([p.detach().reshape(-1) for p in L.policy_net.parameters()])
-    assert float((res["after"] - after).abs().max()) <= 1e-6, "DP-2 step != single-process step"
+    # AdamW's first step is lr g / (|g| + eps) (+ the decay, the same on both sides): equal gradients give equal steps, and the
+    # gradient difference dg admitted above moves an element's step by at most lr eps |dg| / (eps + min |g|)^2 (min |g| over the
+    # segment between the two gradients: 0 when their signs differ).  That is negligible wherever |g| >> eps, but ~1e-8 gradients
+    # are rounding noise whose size depends on the host's BLAS kernels; so 1e-6 plus exactly what the measured dg can cause.
+    lr, eps = (float(L.optimizer.param_groups[0][k]) for k in ("lr", "eps"))
+    g1, g2 = res["grad"].double(), ref.double()
+    lo = th.where(th.sign(g1) == th.sign(g2), th.minimum(g1.abs(), g2.abs()), th.zeros_like(g1))
+    tol = 1e-6 + lr * eps * (g1 - g2).abs() / (eps + lo) ** 2
+    step_err = (res["after"] - after).abs().double()
+    assert bool((step_err <= tol).all()), ("DP-2 step != single-process step", float(step_err.max()),
+                                           float((step_err - tol).max()))
     targ = th.cat([p.detach().reshape(-1) for p in L.target_net.parameters()])
     assert float((res["target"] - targ).abs().max()) <= 1e-6
 
