@@ -7,7 +7,8 @@ import pytest
 import torch as th
 
 from oracle import restatement as R
-from tests.gpu_util import agent_from_params, default_init_params, make_args, synth_graph, to_batch
+from tests.gpu_util import (EXP3, UPDATE_CASES, _exp3_learner_and_sequence, _LibSpy, _oracle_at_gpu_branch,
+                            agent_from_params, default_init_params, make_args, synth_graph, to_batch)
 from tests.util import assert_close, grad_close, load_golden, load_learner_golden, wait_worker
 
 pytestmark = pytest.mark.gpu
@@ -80,10 +81,6 @@ def test_golden_drqn_twin():
     g32 = _oracle32_golden("agent_drqn")
     for k, prm in net.named_parameters():
         grad_close(prm.grad, th.as_tensor(z["grad:" + k]), f"drqn grad {k}", ref32=g32[k], floor=GRAD_FLOOR)
-
-
-EXP3 = dict(enc="gnn", c="tarmac", n_heads=4, key_size=16, msg_size=64, n_rounds=1, n_layers=2, dueling=False,
-            hidden_size=256, n_actions=9)
 
 
 @pytest.mark.parametrize("dist,talk,B,n,M", [("dense", "complete", 16, 8, 80), ("env", "complete", 64, 8, 80),
@@ -2581,118 +2578,7 @@ def test_graphed_cycle_reports_the_loss_of_every_replay_across_device_synchronis
 
 # ---------------------------------------------------------------------------------------------------------------------
 # Round 6: the oracle on the path the benchmark times (learner.update at exp3 sizes with production kernel dispatch)
-
-def _oracle_obs(g, dtype):
-    """Segment-layout dict of a HeteroBatch on the CPU (what oracle/restatement.py reads)."""
-    x_gt, seen_off = g.relation_segments("seen")
-    x_ubs, near_off = g.relation_segments("near")
-    talk_off, talk_src = g.talk_csc()
-    f = lambda t: t.detach().cpu().to(dtype)   # noqa: E731
-    return dict(x_a=f(g.agent_feat()), x_gt=f(x_gt), seen_off=seen_off.cpu(), x_ubs=f(x_ubs), near_off=near_off.cpu(),
-                talk_off=talk_off.cpu(), talk_src=talk_src.cpu())
-
-
-class _LibSpy:
-    """Records the name of every C-ABI entry the product fetches from the library (ops.py calls ``L.lib().<entry>(...)``)."""
-
-    def __init__(self, real):
-        self._real, self.names, self.calls = real, [], []      # calls: (name, positional arguments) of every call made through the spy
-
-    def __getattr__(self, name):
-        self.names.append(name)
-        f = getattr(self._real, name)
-        if not callable(f):
-            return f
-
-        def call(*a):
-            self.calls.append((name, a))
-            return f(*a)
-        return call
-
-
-def _exp3_learner_and_sequence(B, n, M, T, dist, seed):
-    """exp3 learner whose target network differs from the policy (as it does after the first polyak step) and whose biases
-    are not DGL's zeros, + one sampled batch of bench.py's generator."""
-    import bench
-    from uav_bs_ctrl_amd.learner import MultiAgentQLearner
-    th.manual_seed(seed)
-    learner = MultiAgentQLearner(dict(obs_shape=dict(agent=2, ubs=2, gt=4), n_actions=9, n_agents=n, episode_limit=T),
-                                 bench.exp3_args("cuda"))
-    gen = th.Generator(device="cuda").manual_seed(1000 + seed)
-    with th.no_grad():
-        for prm in learner.policy_net.parameters():
-            if prm.dim() == 1:
-                prm.add_(0.05 * th.randn(prm.shape, device="cuda", generator=gen))
-        for pt, pp in zip(learner.target_net.parameters(), learner.policy_net.parameters()):
-            pt.copy_(pp + 0.02 * pp.abs().mean() * th.randn(pp.shape, device="cuda", generator=gen))
-    learner.invalidate_weight_cache()
-    batch = bench.make_sequence(B, n, M, T, dist, th.device("cuda"), seed=7 + seed, distinct=2)
-    batch["h0"] = 0.1 * th.randn(B * n, 256, device="cuda", generator=gen)          # stored hidden states, not zeros
-    return learner, batch
-
-
-class _ScriptedRelu:
-    """Stands in for ``torch.nn.functional`` inside oracle/restatement.py during ONE ``R.madrqn_loss``: ``relu`` records the
-    pre-activation of every call and, where a pattern is prescribed for the call, applies THAT activation pattern (y = x * mask)
-    instead of x > 0.  Calls are identified by their order - three per agent forward (`seen` conv, `near` conv, f_aggr), forwards in
-    the order of learner.py:110-128 (policy t, target t + 1, ..., policy T)."""
-
-    def __init__(self, masks=None):
-        self.masks, self.pre, self.i = masks or {}, [], 0
-
-    def __getattr__(self, name):
-        return getattr(th.nn.functional, name)
-
-    def relu(self, x):
-        m = self.masks.get(self.i)
-        self.pre.append(x.detach())
-        self.i += 1
-        return th.nn.functional.relu(x) if m is None else x * m.to(x.dtype).view_as(x)
-
-
-def _oracle_update(learner, batch, dtype, next_acts=None, relu_masks=None):
-    """loss, policy outputs, the gradient of every policy parameter and the ReLU pre-activations (in call order) from
-    oracle/restatement.py:madrqn_loss on the CPU."""
-    cfg = dict(EXP3)
-    pp = {k: v.detach().cpu().to(dtype).requires_grad_(True) for k, v in learner.policy_net.state_dict().items()}
-    pt = {k: v.detach().cpu().to(dtype) for k, v in learner.target_net.state_dict().items()}
-    obs = [_oracle_obs(g, dtype) for g in batch["obs"]]
-    f = lambda t: t.detach().cpu().to(dtype)   # noqa: E731
-    script, real = _ScriptedRelu(relu_masks), R.F
-    R.F = script
-    try:
-        loss, agent_out, _ = R.madrqn_loss(obs, f(batch["h0"]), f(batch["h1"]), batch["acts"].cpu(), f(batch["rews"]), f(batch["dones"]),
-                                           pp, pt, cfg, learner.gamma, True, next_acts=next_acts)
-    finally:
-        R.F = real
-    names = [k for k, _ in learner.policy_net.named_parameters()]
-    return loss.detach(), agent_out.detach(), dict(zip(names, th.autograd.grad(loss, [pp[k] for k in names]))), script.pre
-
-
-def _gpu_relu_patterns(learner, batch, T, N):
-    """{call index of _ScriptedRelu: activation pattern} of the POLICY forwards as the HIP path evaluated them: the signs of the K1 output
-    halves and of the encoder output on the time-batched graph."""
-    from uav_bs_ctrl_amd import ops
-    enc, g = learner.policy_net.enc, batch["obs_all"].fresh()
-    with th.no_grad():
-        rels = []
-        for et in ("seen", "near"):
-            x_src, off = g.relation_segments(et)
-            rels.append((x_src, off, g.relation_order(et), enc.f_conv[et]))
-        k1 = ops.hetero_gatv2(g.agent_feat(), enc._n_heads, rels)
-        x = ops.linear_relu(k1, enc.f_aggr[0].weight, enc.f_aggr[0].bias)
-    H = x.shape[1]
-    k1, x = (k1 > 0).cpu(), (x > 0).cpu()
-    masks = {}
-    for t in range(T + 1):
-        fwd = 2 * t                                    # policy forward of step t is forward number 2 t (target forwards in between)
-        rows = slice(t * N, (t + 1) * N)
-        masks[3 * fwd], masks[3 * fwd + 1], masks[3 * fwd + 2] = k1[rows, :H], k1[rows, H:], x[rows]
-    return masks
-
-
-UPDATE_CASES = [("1280 rows", 160, 8, 20, 3), ("4096 rows", 512, 8, 10, 2), ("16384 rows", 2048, 8, 6, 1)]
-
+# (helpers: tests/gpu_util.py)
 
 @pytest.mark.parametrize("dist", ["env", "dense"])
 @pytest.mark.parametrize("label,B,n,M,T", UPDATE_CASES)
@@ -2746,33 +2632,8 @@ def test_learner_update_at_exp3_sizes_vs_oracle(label, B, n, M, T, dist, monkeyp
         expect |= {"uavgnn_gru_gates_bwd_fused_sums_rowmax", "uavgnn_gemm_nt_h2_rm2"}      # (d_proj's row maxima inside the d x launch)
         expect -= {"uavgnn_gru_gates_bwd_fused_sums"}
     assert expect <= called, f"{label}: production kernels not dispatched: {sorted(expect - called)}"
-    # --- oracle, float64.  The loss has two kinds of DISCONTINUITIES, at which an fp32 and a float64 evaluation may legitimately part:
-    # the double-Q argmax (learner.py:138) and the ReLU kinks of the encoder (one flipped element of 3 x 10^6 moves a gradient by
-    # 1 / rows = 8e-5 of its unit's value - seen as ONE output unit of f_aggr off by 6e-5 on the 4096-row D-dense batch).  Both sides
-    # are therefore compared at the SAME branch: the choices the HIP path made, after checking that they differ from float64's own only
-    # where float64 itself sits on the discontinuity (top-two Q values / pre-activations within 2e-5 / 1e-5 of the tensor's scale).
-    l64, q64, g64, pre64 = _oracle_update(learner, batch, th.float64)
-    q_gpu = out["QVals"].detach().cpu()
-    assert_close(q_gpu, q64, 1e-5, f"{label} {dist}: QVals")
-    na_gpu, na64 = q_gpu[1:].argmax(2, keepdim=True), q64[1:].argmax(2, keepdim=True)
-    diff = (na_gpu != na64).squeeze(2)
-    if bool(diff.any()):
-        top2 = q64[1:].topk(2, dim=2).values
-        gap = (top2[..., 0] - top2[..., 1])[diff]
-        assert float(gap.max()) <= 2e-5 * float(q64.abs().max()), f"{label} {dist}: argmax differs on rows that do not tie"
-    patterns = _gpu_relu_patterns(learner, batch, T, N)
-    flips = 0
-    for i, m in patterns.items():
-        pre = pre64[i].reshape(m.shape)
-        flipped = (pre > 0) != m
-        if bool(flipped.any()):
-            flips += int(flipped.sum())
-            assert float(pre[flipped].abs().max()) <= 1e-5 * float(pre.abs().max()), \
-                f"{label} {dist}: ReLU pattern of call {i} differs from float64's away from the kink"
-    assert flips <= 1e-5 * sum(m.numel() for m in patterns.values()) + 2, f"{label} {dist}: {flips} ReLU elements flipped"
-    if flips or bool(diff.any()):
-        l64, q64, g64, _ = _oracle_update(learner, batch, th.float64, next_acts=na_gpu, relu_masks=patterns)
-    l32, _, g32, _ = _oracle_update(learner, batch, th.float32, next_acts=na_gpu, relu_masks=patterns)
+    # --- oracle, float64 (float32 for the error floor), at the branch the HIP path took (tests/gpu_util.py: _oracle_at_gpu_branch)
+    l64, _, g64, l32, g32 = _oracle_at_gpu_branch(learner, batch, out["QVals"].detach().cpu(), T, N, f"{label} {dist}")
     assert_close(out["LossQ"], l64, 1e-5, f"{label} {dist}: LossQ")
     off = {id(q): o for q, o in zip(learner.grads.params, learner.grads.offsets)}
     for k, prm in learner.policy_net.named_parameters():

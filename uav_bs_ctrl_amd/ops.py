@@ -142,7 +142,8 @@ class _HeteroGATv2(th.autograd.Function):
                     rmA, rmB = th.empty(N, dtype=th.float32, device=x_dst.device), th.empty(N, dtype=th.float32, device=x_dst.device)
                     rc = lib.uavgnn_gatv2_hetero_fwd_rowmax(*head, L.ptr(image), out.data_ptr(), R * H, L.ptr(aS), L.ptr(aN), rmA.data_ptr(),
                                                             rmB.data_ptr(), phases, L.stream())
-                    _HeteroGATv2.last_rowmax = (out.data_ptr(), rmA, rmB)
+                    if rc == 0:     # a declined launch wrote nothing: the per-relation kernels below fill `out`, and no maxima exist
+                        _HeteroGATv2.last_rowmax = (out.data_ptr(), rmA, rmB)
                 elif image is not None:
                     rc = lib.uavgnn_gatv2_hetero_fwd_image(*head, image.data_ptr(), *tail)
                 else:
@@ -208,8 +209,15 @@ def hetero_gatv2(x_dst, nh, relations):
     out = _HeteroGATv2.apply(x_dst, nh, th.is_grad_enabled(), *flat)
     rm, _HeteroGATv2.last_rowmax = _HeteroGATv2.last_rowmax, None
     if rm is not None and rm[0] == out.data_ptr():
-        out._uavgnn_rowmax = rm[1:]        # (row maxima of the `near` / `seen` halves: read by linear_relu right behind this call)
+        # (row maxima of the `near` / `seen` halves: read by linear_relu right behind this call) + the version counter they hold for:
+        # an in-place edit of `out` in between leaves them stale
+        out._uavgnn_rowmax = (rm[1], rm[2], _version_of(out))
     return out
+
+
+def _version_of(t):
+    """t's version counter (None for an inference tensor, which has none)."""
+    return None if t.is_inference() else t._version
 
 
 def _talk_transpose_if_needed(g, *tensors):
@@ -950,7 +958,7 @@ class _LinearReLU(th.autograd.Function):
 
 def linear_relu(x, W, b):
     rm = getattr(x, "_uavgnn_rowmax", None)      # left by hetero_gatv2 on a time-batched launch
-    if rm is not None:
+    if rm is not None and rm[2] == _version_of(x):   # (only while x is unchanged: a stale bound overflows f16 or drops bits)
         return _LinearReLU.apply(x, W, b, rm[0], rm[1], th.is_grad_enabled())
     return _LinearReLU.apply(x, W, b)
 
