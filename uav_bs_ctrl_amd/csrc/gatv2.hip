@@ -28,6 +28,12 @@ int gatv2_bwd_mfma_launch(const float* x_src, const float* x_dst, const int32_t*
                           const float* W_s, const float* b_s, const float* W_d, const float* b_d, const float* attn, float slope,
                           const float* out, const float* d_out, int ld_out, const float* a_save, float* partial,
                           int onepass_max_deg, int grid, hipStream_t st);
+// defined in gatv2_bwd_mfma.hip: launches gatv2_bwd_resident_kernel (the same class, matrix-core accumulators resident over all
+// destinations of a wavefront); same arguments and partial-row layout, a_save rows 16-byte aligned
+int gatv2_bwd_resident_launch(const float* x_src, const float* x_dst, const int32_t* seg_off, const int32_t* dst_order, int N,
+                              const float* W_s, const float* b_s, const float* W_d, const float* b_d, const float* attn, float slope,
+                              const float* out, const float* d_out, int ld_out, const float* a_save, float* partial,
+                              int onepass_max_deg, int grid, hipStream_t st);
 namespace {
 
 constexpr int kWavesPerBlock = 4;
@@ -1134,8 +1140,15 @@ int launch_bwd(const float* x_src, const float* x_dst, const int32_t* seg_off, c
   if constexpr (FS == 4 && NH == 4 && D == 64) {
     if (mfma && onepass > 0) {
       const int g = capped_grid(N, kWavesPerBlock, kMaxBwdBlocks / 2);
-      int rc = gatv2_bwd_mfma_launch(x_src, x_dst, seg_off, dst_order, N, W_s, b_s, W_d, b_d, attn, slope, out, d_out, ld_out,
-                                     a_save, ws, onepass, g, st);
+      // A/B switch: UAVGNN_K1_BWD_RESIDENT=0 selects the kernel that drains its accumulators after every destination (read at
+      // every call, so that one process can compare the two)
+      const char* res_env = getenv("UAVGNN_K1_BWD_RESIDENT");
+      const bool resident_on = !(res_env && res_env[0] == '0');
+      const bool resident = resident_on && onepass <= 2 * kWave && (reinterpret_cast<uintptr_t>(a_save) & 15) == 0;
+      int rc = resident ? gatv2_bwd_resident_launch(x_src, x_dst, seg_off, dst_order, N, W_s, b_s, W_d, b_d, attn, slope, out, d_out,
+                                                    ld_out, a_save, ws, onepass, g, st)
+                        : gatv2_bwd_mfma_launch(x_src, x_dst, seg_off, dst_order, N, W_s, b_s, W_d, b_d, attn, slope, out, d_out,
+                                                ld_out, a_save, ws, onepass, g, st);
       if (rc) return rc;
       hipLaunchKernelGGL((gatv2_bwd_kernel<FS, NH, D, true, false>), dim3(g), dim3(kThreads), 0, st, x_src, x_dst, seg_off, dst_order,
                          N, W_s, b_s, W_d, b_d, attn, slope, out, d_out, ld_out, a_save, ws + static_cast<size_t>(g) * P, onepass, 2);
