@@ -207,16 +207,28 @@ def edge_conv(g: dict, x, h, p: dict, n_rounds: int = 1):
 # a5: DiscreteComm.forward (gnn_agents.py:180-193).  ``gumbel`` is the per-edge Gumbel(0,1) noise
 # [E, msg, 2] that F.gumbel_softmax draws internally (gnn_agents.py:172); it is an explicit input here so that
 # results are reproducible.  tau=0.5, hard=True, straight-through estimator.
-def disc_comm(g: dict, x, h, p: dict, msg_size: int, gumbel, exact_ties: bool = False):
+def disc_logits(x, h, p: dict):
+    """Per-SOURCE-node logits [N, 2*msg] of DiscreteComm's f_enc (gnn_agents.py:172); an edge reads its source's row."""
+    return F.linear(th.cat((x, h.detach()), 1), p["f_enc.weight"], p["f_enc.bias"])
+
+
+def disc_comm(g: dict, x, h, p: dict, msg_size: int, gumbel, exact_ties: bool = False, hard=None):
     """exact_ties=False reproduces the reference literally: the max (and hence the edge that receives the gradient)
     is taken over the floating-point values (y_hard - y_soft) + y_soft, so ties between several "1" bits are broken by
     rounding noise.  exact_ties=True is the exact-arithmetic rule the HIP kernel implements: the first in-edge whose
-    hard bit is set (else the first in-edge) owns the channel."""
+    hard bit is set (else the first in-edge) owns the channel.
+
+    ``hard`` [E, msg] bool: the hard choice handed in instead of the argmax of this run's own y_soft (True = class 0).  The
+    argmax of (logit + noise) is a discontinuity of the forward: a checker that compares two precisions first verifies that
+    the choices differ only on near-ties, then evaluates both sides at the SAME choice (as ``next_acts`` of madrqn_loss)."""
     src, dst = talk_edges(g)
     n = x.shape[0]
-    logits = F.linear(th.cat((x, h.detach()), 1), p["f_enc.weight"], p["f_enc.bias"]).index_select(0, src)
+    logits = disc_logits(x, h, p).index_select(0, src)
     y_soft = th.softmax((logits.view(-1, msg_size, 2) + gumbel) / 0.5, -1)
-    idx = y_soft.max(-1, keepdim=True)[1]
+    if hard is None:
+        idx = y_soft.max(-1, keepdim=True)[1]
+    else:
+        idx = (~hard.view(-1, msg_size, 1).to(th.bool)).long()
     y_hard = th.zeros_like(y_soft).scatter_(-1, idx, 1.0)
     m = (y_hard - y_soft.detach() + y_soft).flatten(1)               # [E, 2*msg]
     if exact_ties:
@@ -239,10 +251,11 @@ def q_head(h, p: dict, dueling: bool):
 # --------------------------------------------------------------------------------------------------------------------
 # a1: GnnAgent.forward (gnn_agents.py:51-56)
 
-def gnn_agent_forward(g: dict, h, p: dict, cfg: dict, gumbel=None):
+def gnn_agent_forward(g: dict, h, p: dict, cfg: dict, gumbel=None, hard=None):
     """g: dict of segment-layout arrays (x_gt, seen_off, x_ubs, near_off, x_a, talk_off, talk_src) or, for the
     dense encoder, ``x_flat``.  p: state_dict of the reference module.  cfg: n_heads, c, key_size, msg_size,
-    n_rounds, n_layers, dueling, enc ('gnn'|'mlp').  Returns (q, h')."""
+    n_rounds, n_layers, dueling, enc ('gnn'|'mlp').  gumbel / hard: DiscreteComm's noise and optional hard-bit override
+    (disc_comm).  Returns (q, h')."""
     if cfg.get("enc", "gnn") == "gnn":
         x = graph_obs_encoder(g, sub(p, "enc"), cfg["n_heads"])
     else:
@@ -253,7 +266,7 @@ def gnn_agent_forward(g: dict, h, p: dict, cfg: dict, gumbel=None):
     elif c == "tarmac":
         h = tarmac(g, x, h, sub(p, "f_comm"), cfg["key_size"], cfg.get("n_rounds", 1))
     elif c == "disc":
-        h = disc_comm(g, x, h, sub(p, "f_comm"), cfg["msg_size"], gumbel, cfg.get("exact_ties", False))
+        h = disc_comm(g, x, h, sub(p, "f_comm"), cfg["msg_size"], gumbel, cfg.get("exact_ties", False), hard=hard)
     elif c == "base":
         h = base_comm(g, x, h, sub(p, "f_comm"))
     elif c == "commnet":
@@ -276,7 +289,8 @@ def drqn_gnn_agent_forward(g: dict, h, p: dict, n_heads: int):
 # --------------------------------------------------------------------------------------------------------------------
 # row L: the BPTT pattern of MultiAgentQLearner.update (learner.py:110-154), loss only (no optimiser).
 
-def madrqn_loss(obs, h0, h1, acts, rews, dones, p_policy, p_target, cfg, gamma, double_q=True, next_acts=None):
+def madrqn_loss(obs, h0, h1, acts, rews, dones, p_policy, p_target, cfg, gamma, double_q=True, next_acts=None, gumbels=None,
+                hard_bits=None):
     """obs: list of T+1 graph dicts; acts [T, B*n, 1] long; rews/dones broadcastable to [T, B, n].
 
     ``next_acts`` [T, B*n, 1] long: the double-Q action choice handed in instead of the argmax over this run's own policy
@@ -284,17 +298,23 @@ def madrqn_loss(obs, h0, h1, acts, rews, dones, p_policy, p_target, cfg, gamma, 
     a checker that compares two precisions first verifies that the two choices differ only on rows whose top-two Q values tie
     to within the comparison's tolerance, then evaluates both sides under the SAME choice.
 
+    ``gumbels`` / ``hard_bits``: per-forward lists (DiscreteComm's [E, msg, 2] noise and optional [E, msg] hard-bit override,
+    see disc_comm), in the call order of the loop below: policy t, target t + 1, ..., policy T (forward k = 2 t is the policy
+    at step t, k = 2 t + 1 the target at step t + 1).  An entry of hard_bits may be None (the forward's own argmax).
+
     Returns (loss, agent_out [T+1, N_a, A], target_out [T, N_a, A])."""
     T = len(obs) - 1
     h, h_t = h0, h1
     agent_out, target_out = [], []
+    kw = lambda k: dict(gumbel=None if gumbels is None else gumbels[k],   # noqa: E731
+                        hard=None if hard_bits is None else hard_bits[k])
     for t in range(T):
-        q, h = gnn_agent_forward(obs[t], h, p_policy, cfg)
+        q, h = gnn_agent_forward(obs[t], h, p_policy, cfg, **kw(2 * t))
         agent_out.append(q)
         with th.no_grad():
-            qn, h_t = gnn_agent_forward(obs[t + 1], h_t, p_target, cfg)
+            qn, h_t = gnn_agent_forward(obs[t + 1], h_t, p_target, cfg, **kw(2 * t + 1))
             target_out.append(qn)
-    q, h = gnn_agent_forward(obs[T], h, p_policy, cfg)
+    q, h = gnn_agent_forward(obs[T], h, p_policy, cfg, **kw(2 * T))
     agent_out.append(q)
     agent_out, target_out = th.stack(agent_out), th.stack(target_out)
     qvals = agent_out[:-1].gather(2, acts)

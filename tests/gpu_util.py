@@ -118,14 +118,14 @@ class _LibSpy:
         return call
 
 
-def _exp3_learner_and_sequence(B, n, M, T, dist, seed):
+def _exp3_learner_and_sequence(B, n, M, T, dist, seed, c="tarmac"):
     """exp3 learner whose target network differs from the policy (as it does after the first polyak step) and whose biases
-    are not DGL's zeros, + one sampled batch of bench.py's generator."""
+    are not DGL's zeros, + one sampled batch of bench.py's generator.  c: the communication variant of run_exp3.py's grid."""
     import bench
     from uav_bs_ctrl_amd.learner import MultiAgentQLearner
     th.manual_seed(seed)
     learner = MultiAgentQLearner(dict(obs_shape=dict(agent=2, ubs=2, gt=4), n_actions=9, n_agents=n, episode_limit=T),
-                                 bench.exp3_args("cuda"))
+                                 bench.exp3_args("cuda", c=c))
     gen = th.Generator(device="cuda").manual_seed(1000 + seed)
     with th.no_grad():
         for prm in learner.policy_net.parameters():
@@ -158,21 +158,29 @@ class _ScriptedRelu:
         return th.nn.functional.relu(x) if m is None else x * m.to(x.dtype).view_as(x)
 
 
-def _oracle_update(learner, batch, dtype, next_acts=None, relu_masks=None):
+def _oracle_update(learner, batch, dtype, next_acts=None, relu_masks=None, cfg=None, gumbels=None, hard_bits=None, disc_logits=None):
     """loss, policy outputs, the gradient of every policy parameter and the ReLU pre-activations (in call order) from
-    oracle/restatement.py:madrqn_loss on the CPU."""
-    cfg = dict(EXP3)
+    oracle/restatement.py:madrqn_loss on the CPU.  cfg: the oracle's configuration (default EXP3); gumbels / hard_bits: DiscreteComm's
+    per-forward noise and hard-bit override (R.madrqn_loss); disc_logits: a list that receives the per-EDGE logits [E, 2 msg] of every
+    DiscreteComm forward, in call order."""
+    cfg = dict(EXP3) if cfg is None else dict(cfg)
     pp = {k: v.detach().cpu().to(dtype).requires_grad_(True) for k, v in learner.policy_net.state_dict().items()}
     pt = {k: v.detach().cpu().to(dtype) for k, v in learner.target_net.state_dict().items()}
     obs = [_oracle_obs(g, dtype) for g in batch["obs"]]
     f = lambda t: t.detach().cpu().to(dtype)   # noqa: E731
-    script, real = _ScriptedRelu(relu_masks), R.F
+    script, real, real_dc = _ScriptedRelu(relu_masks), R.F, R.disc_comm
+
+    def disc_spy(g, x, h, p, *a, **k):
+        disc_logits.append(R.disc_logits(x, h, p).detach().index_select(0, R.talk_edges(g)[0]))
+        return real_dc(g, x, h, p, *a, **k)
     R.F = script
+    if disc_logits is not None:
+        R.disc_comm = disc_spy
     try:
         loss, agent_out, _ = R.madrqn_loss(obs, f(batch["h0"]), f(batch["h1"]), batch["acts"].cpu(), f(batch["rews"]), f(batch["dones"]),
-                                           pp, pt, cfg, learner.gamma, True, next_acts=next_acts)
+                                           pp, pt, cfg, learner.gamma, True, next_acts=next_acts, gumbels=gumbels, hard_bits=hard_bits)
     finally:
-        R.F = real
+        R.F, R.disc_comm = real, real_dc
     names = [k for k, _ in learner.policy_net.named_parameters()]
     return loss.detach(), agent_out.detach(), dict(zip(names, th.autograd.grad(loss, [pp[k] for k in names]))), script.pre
 
@@ -202,22 +210,34 @@ def _gpu_relu_patterns(learner, batch, T, N):
 UPDATE_CASES = [("1280 rows", 160, 8, 20, 3), ("4096 rows", 512, 8, 10, 2), ("16384 rows", 2048, 8, 6, 1)]
 
 
-def _oracle_at_gpu_branch(learner, batch, q_gpu, T, N, what):
+def _oracle_at_gpu_branch(learner, batch, q_gpu, T, N, what, cfg=None, disc=None, stats=None):
     """(loss, Q values, gradients) of the float64 oracle and (loss, gradients) of the float32 oracle for ONE batch, evaluated at the
     branch the HIP path took.  The loss has two kinds of DISCONTINUITIES, at which an fp32 and a float64 evaluation may legitimately part:
     the double-Q argmax (learner.py:138) and the ReLU kinks of the encoder (one flipped element of 3 x 10^6 moves a gradient by
     1 / rows = 8e-5 of its unit's value - seen as ONE output unit of f_aggr off by 6e-5 on the 4096-row D-dense batch).  Both sides
     are therefore compared at the SAME branch: the choices the HIP path made, after checking that they differ from float64's own only
     where float64 itself sits on the discontinuity (top-two Q values / pre-activations within 2e-5 / 1e-5 of the tensor's scale).
-    q_gpu: the HIP path's Q values of this batch (CPU), asserted against float64 on the way."""
-    l64, q64, g64, pre64 = _oracle_update(learner, batch, th.float64)
+    q_gpu: the HIP path's Q values of this batch (CPU), asserted against float64 on the way.
+
+    cfg: the oracle's configuration (default EXP3).  disc (c = "disc"): dict(gumbels=[...], bits=[...]) per DiscreteComm forward in call
+    order - the kernel's own noise and the hard bits it chose ([E, msg] bool, True = class 0).  Each bit is an argmax of (logit + noise), a
+    third discontinuity: float64 is evaluated AT the kernel's bits, and at every forward its own choice from its own logits must differ
+    from the kernel's only where |(l0 + g0) - (l1 + g1)| <= 2e-5 of the forward's logit scale (max |logit|).  stats: a dict that
+    receives, per kind of decision (argmax / relu / bits), how many were taken at the HIP path's branch against float64's own choice
+    and the largest float64 margin among them relative to the scale it was judged against."""
+    hb = None if disc is None else disc["bits"]
+    gum = lambda dt: None if disc is None else [g.to(dt) for g in disc["gumbels"]]   # noqa: E731
+    trace = None if disc is None else []
+    l64, q64, g64, pre64 = _oracle_update(learner, batch, th.float64, cfg=cfg, gumbels=gum(th.float64), hard_bits=hb, disc_logits=trace)
     assert_close(q_gpu, q64, 1e-5, f"{what}: QVals")
+    st = dict(argmax=0, argmax_margin=0.0, relu=0, relu_margin=0.0, relu_total=0, bits=0, bits_margin=0.0, bits_total=0)
     na_gpu, na64 = q_gpu[1:].argmax(2, keepdim=True), q64[1:].argmax(2, keepdim=True)
     diff = (na_gpu != na64).squeeze(2)
     if bool(diff.any()):
         top2 = q64[1:].topk(2, dim=2).values
         gap = (top2[..., 0] - top2[..., 1])[diff]
         assert float(gap.max()) <= 2e-5 * float(q64.abs().max()), f"{what}: argmax differs on rows that do not tie"
+        st["argmax"], st["argmax_margin"] = int(diff.sum()), float(gap.max()) / float(q64.abs().max())
     patterns = _gpu_relu_patterns(learner, batch, T, N)
     flips = 0
     for i, m in patterns.items():
@@ -227,8 +247,29 @@ def _oracle_at_gpu_branch(learner, batch, q_gpu, T, N, what):
             flips += int(flipped.sum())
             assert float(pre[flipped].abs().max()) <= 1e-5 * float(pre.abs().max()), \
                 f"{what}: ReLU pattern of call {i} differs from float64's away from the kink"
+            st["relu_margin"] = max(st["relu_margin"], float(pre[flipped].abs().max()) / float(pre.abs().max()))
     assert flips <= 1e-5 * sum(m.numel() for m in patterns.values()) + 2, f"{what}: {flips} ReLU elements flipped"
+    st["relu"], st["relu_total"] = flips, sum(m.numel() for m in patterns.values())
+    if disc is not None:
+        assert len(trace) == len(hb) == 2 * T + 1, f"{what}: {len(trace)} DiscreteComm forwards in the oracle, {len(hb)} on the GPU"
+        for k, (lg, g, bits) in enumerate(zip(trace, disc["gumbels"], hb)):
+            lg = lg.view(bits.shape[0], -1, 2)
+            margin = (lg[..., 0] + g[..., 0].double()) - (lg[..., 1] + g[..., 1].double())
+            own = margin >= 0                        # class 0 wins a tie (torch.max and the kernel's y0 >= y1)
+            other = own != bits
+            st["bits_total"] += bits.numel()
+            if bool(other.any()):
+                scale = float(lg.abs().max())
+                worst = float(margin[other].abs().max())
+                assert worst <= 2e-5 * scale, f"{what}: hard bit of forward {k} differs from float64's away from the tie ({worst:.3e} of {scale:.3e})"
+                st["bits"] += int(other.sum())
+                st["bits_margin"] = max(st["bits_margin"], worst / scale)
+        assert st["bits"] <= 1e-5 * st["bits_total"] + 2, f"{what}: {st['bits']} hard bits differ from float64's"
+    if stats is not None:
+        stats.update(st)
     if flips or bool(diff.any()):
-        l64, q64, g64, _ = _oracle_update(learner, batch, th.float64, next_acts=na_gpu, relu_masks=patterns)
-    l32, _, g32, _ = _oracle_update(learner, batch, th.float32, next_acts=na_gpu, relu_masks=patterns)
+        l64, q64, g64, _ = _oracle_update(learner, batch, th.float64, next_acts=na_gpu, relu_masks=patterns, cfg=cfg, gumbels=gum(th.float64),
+                                          hard_bits=hb)
+    l32, _, g32, _ = _oracle_update(learner, batch, th.float32, next_acts=na_gpu, relu_masks=patterns, cfg=cfg, gumbels=gum(th.float32),
+                                    hard_bits=hb)
     return l64, q64, g64, l32, g32

@@ -3054,6 +3054,41 @@ def test_gemm_tn_f16x2_weight_gradient_vs_float64(n, Mo, Ko, views, bounds):
     assert th.equal(part2.sum(0), got)
 
 
+@pytest.mark.parametrize("n,Mo,Ko", [(65536, 260, 132)])
+def test_gemm_tn_f16x2_global_bound_column_ladder(n, Mo, Ko):
+    """csrc/gemm_tn_h2.hip under ONE global bound per operand, as WeightGradSink.end_sequence passes it, with columns 2^-17, 2^-24, 2^-30
+    and 2^-40 below that bound: every entry within the derived floor |dW - ref| <= A sum|dy||x| + B_FLOOR (B_y sum|x| + B_x sum|dy|)
+    against float64 (constants and derivation: tests/test_f16x2_emulation.py; A = A_GPU includes the fp32 accumulation)."""
+    import json
+    import os
+    from tests.test_f16x2_emulation import A_GPU, LADDER, derived_bound, ladder_operands
+    from tests.util import _GRAD_LOG
+    from uav_bs_ctrl_amd import _lib as L
+    lib = L.lib()
+    assert lib.uavgnn_gemm_tn_h2_supported(n, Mo, Ko)
+    dy_np, x_np = ladder_operands(n, Mo, Ko, seed=5)
+    dy, x = th.from_numpy(dy_np).cuda(), th.from_numpy(x_np).cuda()
+    cy, cx = dy.abs().max().expand(Mo).contiguous(), x.abs().max().expand(Ko).contiguous()
+    S = lib.uavgnn_gemm_tn_h2_chunks(n, Mo, Ko)
+    part = th.full((S, Mo, Ko), float("nan"), device="cuda")
+    L.check(lib.uavgnn_gemm_tn_h2(dy.data_ptr(), dy.stride(0), Mo, x.data_ptr(), x.stride(0), Ko, n, cy.data_ptr(), cx.data_ptr(),
+                                  part.data_ptr(), S, 0, L.stream()), "gemm_tn_h2")
+    got = part.sum(0).double().cpu().numpy()
+    ref = dy_np.astype("float64").T @ x_np.astype("float64")
+    bound = derived_bound(dy_np, x_np, float(cy[0]), float(cx[0]), A_GPU)
+    ratio = abs(got - ref) / bound
+    rows = {}
+    for i, k in enumerate((0,) + LADDER):         # worst ratio per ladder rung (rows or columns of that rung)
+        rows[f"2^-{k}"] = float(max(ratio[i::5, :].max(), ratio[:, i::5].max()))
+    try:
+        with open(os.path.join(os.path.dirname(_GRAD_LOG), "h2_errors.jsonl"), "a") as f:      # (the directory of the gradient-error log)
+            f.write(json.dumps(dict(test="gemm_tn global-bound ladder", n=n, Mo=Mo, Ko=Ko, worst_ratio_to_floor=rows)) + "\n")
+    except OSError:
+        pass
+    assert (ratio <= 1.0).all(), (f"f16x2 weight gradient outside the derived floor: {rows}; worst entry "
+                                  f"{divmod(int(ratio.argmax()), Ko)}")
+
+
 def test_time_batched_linear_relu_weight_gradient_on_the_f16x2_kernel(monkeypatch):
     """ops.linear_relu (f_aggr, gnn_agents.py:99-102) over 2^18 time-batched rows: the forward GEMM leaves the row maxima of its input, the
     ReLU-backward kernel those of the masked gradient, dx and dW run on the f16x2 kernels (csrc/gemm_h2.hip, csrc/gemm_tn_h2.hip) - against
