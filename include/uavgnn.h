@@ -278,6 +278,25 @@ int uavgnn_relu_bwd_colsum_rowmax(const float* dy, long long ld, const float* y,
 int uavgnn_relu_bwd_colsum(const float* dy, long long ld, const float* y, long long ldy, float* out, long long ldo, int N, int C,
                            float* acc, int S, uavgnn_stream_t stream);
 
+/* ---- first encoder layer on flattened observations (csrc/flat_obs.hip) ---------------------------------------------
+ * Linear(F, H_out) + ReLU of the o = 'mlp' agents (rnn_agents.py:15-18, gnn_agents.py:62-77) read straight from the padded
+ * observation tensors: row r of the flattened observation is [agent[r] (F_a) || gt[r] (K_g = M Sg) || ubs[r] (K_u = (n-1) 3)]
+ * (gym 0.21's sorted Dict keys), the three pieces at agent + r ld_a, gt + r ld_g, ubs + r ld_u (floats;
+ * unit column stride); F = F_a + K_g + K_u.  The [rows, F] concatenation is never written.  fp32 FMA in a fixed order.
+ *   _supported     1 when H_out is 64, 128 or 256 and 1 <= F <= 1024 (else the entries return UAVGNN_EUNSUPPORTED)
+ *   _fwd           y [rows, H_out] (row stride ld_y) = ReLU(x W^T + b); W [H_out, F] contiguous, b [H_out] or NULL
+ *   _wgrad_chunks  the row-chunk count S the caller should use for _wgrad
+ *   _wgrad         partials [S, H_out, F] (+)= per row chunk sum of dy[r]^T x[r] (dy: the ReLU-masked gradient, row stride ld_dy;
+ *                  uavgnn_relu_bwd_colsum gives it and the bias gradient).  The caller sums over S in a fixed order: deterministic. */
+int uavgnn_flat_obs_supported(int H_out, int F);
+int uavgnn_flat_obs_fwd(const float* agent, long long ld_a, int F_a, const float* gt, long long ld_g, int K_g, const float* ubs,
+                        long long ld_u, int K_u, int rows, const float* W, const float* b, int H_out, float* y, long long ld_y,
+                        uavgnn_stream_t stream);
+int uavgnn_flat_obs_wgrad_chunks(long long rows, int H_out, int F);
+int uavgnn_flat_obs_wgrad(const float* dy, long long ld_dy, int H_out, const float* agent, long long ld_a, int F_a, const float* gt,
+                          long long ld_g, int K_g, const float* ubs, long long ld_u, int K_u, int rows, float* partials, int S,
+                          int accumulate, uavgnn_stream_t stream);
+
 /* ---- K3b, per-graph formulation ---------------------------------------------------------------------------------
  * Same contract and arithmetic as uavgnn_talk_attn_fwd / _bwd for a batch of B SMALL graphs (what dgl.batch of
  * per-environment graphs gives: common.py:45, env_wrappers.py:139-154): graph_off[B+1] = agent-node boundaries, every

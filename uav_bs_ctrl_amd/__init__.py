@@ -4,8 +4,9 @@ Drop-in for the reference's ``REGISTRY['gnn']`` (algos/madrqn/agents/__init__.py
 ``forward(g, h) -> (q, h')``, same ``state_dict`` layout; the graph arithmetic runs in hand-written HIP kernels behind
 the C-ABI of ``include/uavgnn.h``.  There is no CPU fallback.
 """
-from .agents import REGISTRY, GnnAgent  # noqa: F401
+from .agents import REGISTRY, GnnAgent, RnnAgent  # noqa: F401
 from .tuned import enable_tuned_gemms  # noqa: F401  (opt-in, process-wide: see uav_bs_ctrl_amd/tuned)
-from .graph import HeteroBatch, batch, cat, from_obs_dicts, from_padded_obs, heterograph, merge  # noqa: F401
+from .graph import (FlatObsBatch, HeteroBatch, batch, cat, from_obs_dicts, from_padded_obs, from_padded_obs_flat,  # noqa: F401
+                    heterograph, merge)
 
 __version__ = "0.1.0"

@@ -15,7 +15,7 @@ import torch as th
 import torch.nn as nn
 
 from .. import ops
-from ..graph import HeteroBatch, RelationView
+from ..graph import FlatObsBatch, HeteroBatch, RelationView
 from .heads import DuelingLayer
 
 
@@ -95,7 +95,22 @@ class DenseObservationEncoder(nn.Module):
         self.enc = nn.Sequential(*layers)
 
     def forward(self, g: HeteroBatch, x=None):
+        if isinstance(g, FlatObsBatch):     # padded views: the first layer reads them in place (csrc/flat_obs.hip)
+            return mlp_encode(self.enc, g)
         return self.enc(g.agent_feat())
+
+
+def mlp_encode(enc: nn.Sequential, obs):
+    """The Linear + ReLU stack of the flattened-observation encoders on a ``FlatObsBatch`` (first layer: ops.flat_linear_relu on the
+    padded pieces) or on an [N, F] tensor (ops.linear_relu throughout)."""
+    lins = [m for m in enc if isinstance(m, nn.Linear)]
+    if isinstance(obs, FlatObsBatch):
+        x = ops.flat_linear_relu(obs.parts, lins[0].weight, lins[0].bias)
+    else:
+        x = ops.linear_relu(obs, lins[0].weight, lins[0].bias)
+    for lin in lins[1:]:
+        x = ops.linear_relu(x, lin.weight, lin.bias)
+    return x
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -105,6 +120,13 @@ def _gru(cell: nn.GRUCell, i_parts, h):
     partial products would."""
     inp = i_parts[0] if len(i_parts) == 1 else th.cat(i_parts, 1)
     return ops.gru_cell(inp, h, cell)     # K4: one fused launch when the shape has an instantiation
+
+
+def _head(f_out, h):
+    """Q head (gnn_agents.py:43-46,:56)."""
+    if isinstance(f_out, DuelingLayer):
+        return f_out(h)
+    return ops.linear(h, f_out.weight, f_out.bias)
 
 
 def _parent(g) -> HeteroBatch:
@@ -344,9 +366,7 @@ class GnnAgent(nn.Module):
             h = self.f_comm(g["talk"], x, h)
         else:
             h = _gru(self.rnn, (x,), h)
-        if isinstance(self.f_out, DuelingLayer):
-            return self.f_out(h), h
-        return ops.linear(h, self.f_out.weight, self.f_out.bias), h
+        return _head(self.f_out, h), h
 
     def _tarmac_step(self, g, x, h, dx_out=None):
         comm = self.f_comm

@@ -650,3 +650,130 @@ def from_padded_obs(gt: th.Tensor, ubs: th.Tensor, agent: th.Tensor, d_u2u: Opti
                 "uavgnn_talk_compact")
         kw.update(talk_off=talk_off, talk_src=talk_src, talk_eid=talk_eid)
     return HeteroBatch.from_arrays(device=dev, **kw)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Flattened observations (exp2's o='mlp').  The reference flattens each agent's observation dict with gym 0.21's `flatten`
+# (FlattenedObservation over the Dict space of mubs_cov.py:70-74), and gym 0.21's spaces.Dict SORTS the keys of a plain dict:
+# a row is agent (2) || gt (M Sg, row-major) || ubs ((n-1) 3, row-major) - DESIGN.md section 3.
+FLAT_OBS_ORDER = ("agent", "gt", "ubs")
+
+
+def _rows2d(t: th.Tensor, N: int) -> th.Tensor:
+    """[N, K] rows of a [B, n, ...] padded field: a view with its row stride when one exists, else a contiguous copy."""
+    K = int(np.prod(t.shape[2:]))
+    try:
+        v = t.view(N, K)
+    except RuntimeError:
+        v = t.reshape(N, K)
+    return v if K <= 1 or v.stride(1) == 1 else v.contiguous()
+
+
+class _FlatFrame(dict):
+    """Node frame of a flattened-observation batch: 'feat' ([N, F] in FLAT_OBS_ORDER) is materialised on first access only - by indexing,
+    ``in``, ``get`` or any iteration over the frame."""
+
+    def __init__(self, parts):
+        super().__init__()
+        self._parts = parts
+
+    def _ensure(self):
+        if not dict.__contains__(self, "feat"):
+            dict.__setitem__(self, "feat", th.cat(self._parts, 1))
+
+    def __contains__(self, key):
+        return key == "feat" or dict.__contains__(self, key)
+
+    def __getitem__(self, key):
+        if key == "feat":
+            self._ensure()
+        return dict.__getitem__(self, key)
+
+    def get(self, key, default=None):
+        return self[key] if key in self else default
+
+    def __iter__(self):
+        self._ensure()
+        return dict.__iter__(self)
+
+    def __len__(self):
+        self._ensure()
+        return dict.__len__(self)
+
+    def keys(self):
+        self._ensure()
+        return dict.keys(self)
+
+    def values(self):
+        self._ensure()
+        return dict.values(self)
+
+    def items(self):
+        self._ensure()
+        return dict.items(self)
+
+
+class FlatObsBatch(HeteroBatch):
+    """A batch of flattened observations: the `talk` relation (when built with d_u2u) and NO `seen` / `near` relations.  The
+    padded pieces stay as row views ``parts`` = (agent [N, 2], gt [N, M Sg], ubs [N, (n-1) 3]) - what the fused first encoder
+    layer reads (ops.flat_linear_relu); ``agent_feat()`` / ``ndata['feat']['agent']`` concatenate them in FLAT_OBS_ORDER on
+    demand (the [N, F] tensor env_wrappers.py:134 writes)."""
+
+    def __init__(self, parts, rels, graph_off=None, hints=None):
+        self.parts = tuple(parts)
+        super().__init__({"agent": self.parts[0].shape[0]}, rels, {"agent": _FlatFrame(self.parts)}, graph_off, hints)
+
+    @property
+    def device(self):
+        return self.parts[0].device
+
+    def to(self, device, non_blocking: bool = True) -> "FlatObsBatch":
+        device = th.device(device)
+        cur = self.device
+        if cur.type == device.type and (device.index is None or device.index == cur.index):
+            return self
+        go = None if self.graph_off is None else self.graph_off.to(device)
+        return FlatObsBatch([p.to(device, non_blocking=non_blocking) for p in self.parts],
+                            {c: r.to(device) for c, r in self._rels.items()}, go, self.hints)
+
+    def fresh(self) -> "FlatObsBatch":
+        return FlatObsBatch(self.parts, self._rels, self.graph_off, self.hints)
+
+    def slice_agents(self, lo: int, hi: int) -> "FlatObsBatch":
+        """Rows [lo, hi) as views (a span of time steps of a time-batched batch); the per-step talk relation is not carried over."""
+        return FlatObsBatch([p[lo:hi] for p in self.parts], {})
+
+
+def from_padded_obs_flat(gt: th.Tensor, ubs: th.Tensor, agent: th.Tensor, d_u2u: Optional[th.Tensor] = None,
+                         r_comm: float = float("inf"), static: bool = False) -> FlatObsBatch:
+    """Sibling of ``from_padded_obs`` for flattened observations: gt [B,n,M,Sg], ubs [B,n,n-1,3], agent [B,n,2], d_u2u [B,n,n] on
+    the GPU.  No observation data is copied (row views of the padded tensors are kept; a field without a uniform row stride is
+    made contiguous once); the talk relation is built by the same HIP passes as ``from_padded_obs`` (same arrays, bit for bit).
+    static=True: talk arrays at capacity (B n n), no host round trip - what a hipGraph capture needs."""
+    from . import _lib as L
+    L.require_gpu(gt, ubs, agent, d_u2u)
+    B, n = gt.shape[0], gt.shape[1]
+    N = B * n
+    dev = gt.device
+    fields = dict(agent=agent, gt=gt, ubs=ubs)
+    parts = [_rows2d(fields[k] if fields[k].dtype == th.float32 else fields[k].float(), N) for k in FLAT_OBS_ORDER]
+    rels = {}
+    if d_u2u is not None:
+        i32 = dict(dtype=th.int32, device=dev)
+        d_u2u = L.f32c(d_u2u)
+        rc = float(min(r_comm, 3.0e38))
+        deg_t, env_e = th.empty(N, **i32), th.empty(B, **i32)
+        L.check(L.lib().uavgnn_talk_degrees(d_u2u.data_ptr(), n, B, rc, deg_t.data_ptr(), env_e.data_ptr(), L.stream()),
+                "uavgnn_talk_degrees")
+        talk_off, env_base = th.empty(N + 1, **i32), th.empty(B + 1, **i32)
+        for off, deg in ((talk_off, deg_t), (env_base, env_e)):
+            off[:1].zero_()                 # a memset: capturable (an indexed scalar store is a host-to-device copy)
+            th.cumsum(deg, 0, out=off[1:])
+        Et = N * n if static else int(talk_off[-1])       # the one host sync of a non-static build: the edge count
+        alloc = th.zeros if static else th.empty
+        talk_src, talk_eid = alloc(Et, **i32), alloc(Et, **i32)
+        L.check(L.lib().uavgnn_talk_compact(d_u2u.data_ptr(), n, B, rc, talk_off.data_ptr(), env_base.data_ptr(),
+                                            talk_src.data_ptr(), talk_eid.data_ptr(), L.stream()), "uavgnn_talk_compact")
+        rels[TALK] = _Relation(talk_off, talk_src, talk_eid)
+    return FlatObsBatch(parts, rels, _uniform_graph_off(N, n, dev),
+                        {"max_graph_agents": n, **({"static": 1} if static else {})})

@@ -15,7 +15,14 @@ from typing import Dict, Optional
 import torch as th
 
 from . import _lib as L
-from .graph import from_padded_obs
+from .graph import from_padded_obs, from_padded_obs_flat
+
+
+def _builder(enc: str):
+    """Device builder of the observation batches: graphs ('gnn', exp3) or flattened observations ('mlp', exp2)."""
+    if enc not in ("gnn", "mlp"):
+        raise ValueError(f"enc must be 'gnn' or 'mlp', got {enc!r}")
+    return from_padded_obs_flat if enc == "mlp" else from_padded_obs
 
 
 def _capture(graph, **kw):
@@ -73,10 +80,13 @@ class GraphedAct:
 
         ga = GraphedAct(learner, B, n, M, r_comm)
         acts, h = ga(gt, ubs, agent, d_u2u, h, eps)        # acts [B*n] int64, h' [B*n, H]; both are the graph's buffers
+
+    enc='mlp': flattened-observation batches (exp2) instead of observation graphs.
     """
 
-    def __init__(self, learner, B: int, n: int, M: int, r_comm: float = float("inf"), warmup: int = 2):
+    def __init__(self, learner, B: int, n: int, M: int, r_comm: float = float("inf"), warmup: int = 2, enc: str = "gnn"):
         self.learner, self.B, self.n, self.M, self.r_comm = learner, B, n, M, r_comm
+        self._build = _builder(enc)
         dev = learner.device
         with_comm = learner.args.c is not None
         self.obs = _PaddedObs((B,), n, M, dev, with_comm)
@@ -98,7 +108,7 @@ class GraphedAct:
     @th.no_grad()
     def _body(self):
         lr = self.learner
-        g = from_padded_obs(self.obs.gt, self.obs.ubs, self.obs.agent, self.obs.d_u2u, self.r_comm, static=True)
+        g = self._build(self.obs.gt, self.obs.ubs, self.obs.agent, self.obs.d_u2u, self.r_comm, static=True)
         logits, h = lr.policy_net(g, self.h_in)
         N = logits.shape[0]
         u = th.rand(self.B + N, device=lr.device, generator=lr._gen)
@@ -139,12 +149,14 @@ class GraphedUpdate:
     """
 
     def __init__(self, learner, B: int, T: int, n: int, M: int, r_comm: float = float("inf"), rew_dim: Optional[int] = None,
-                 warmup: int = 2):
+                 warmup: int = 2, enc: str = "gnn"):
         assert learner.fused_tail, "graph capture needs the device-resident update tail (CUDA learner)"
         self.learner, self.B, self.T, self.n, self.M, self.r_comm = learner, B, T, n, M, r_comm
+        self._build = _builder(enc)      # enc='mlp': flattened-observation batches (exp2)
         dev, H = learner.device, learner.args.hidden_size
         rd = n if rew_dim is None else rew_dim
-        self.obs = _PaddedObs((T + 1, B), n, M, dev, True)        # time-major: step t of every sequence is contiguous
+        # time-major: step t of every sequence is contiguous.  enc='mlp' without communication (RnnAgent) reads no talk relation
+        self.obs = _PaddedObs((T + 1, B), n, M, dev, enc == "gnn" or learner.args.c is not None)
         self.h0 = th.zeros(B * n, H, dtype=th.float32, device=dev)
         self.h1 = th.zeros(B * n, H, dtype=th.float32, device=dev)
         self.acts = th.zeros(T, B * n, 1, dtype=th.int64, device=dev)
@@ -186,10 +198,12 @@ class GraphedUpdate:
     def _batch(self) -> Dict:
         T, B, n, M = self.T, self.B, self.n, self.M
         o = self.obs
-        obs = [from_padded_obs(o.gt[t], o.ubs[t], o.agent[t], o.d_u2u[t], self.r_comm, static=True) for t in range(T + 1)]
+        build = self._build
+        obs = [build(o.gt[t], o.ubs[t], o.agent[t], None if o.d_u2u is None else o.d_u2u[t], self.r_comm, static=True)
+               for t in range(T + 1)]
         flat = lambda x, lo: x[lo:].reshape((-1,) + x.shape[2:])  # noqa: E731
-        obs_all = from_padded_obs(flat(o.gt, 0), flat(o.ubs, 0), flat(o.agent, 0), None, self.r_comm, static=True)
-        obs_next = from_padded_obs(flat(o.gt, 1), flat(o.ubs, 1), flat(o.agent, 1), None, self.r_comm, static=True)
+        obs_all = build(flat(o.gt, 0), flat(o.ubs, 0), flat(o.agent, 0), None, self.r_comm, static=True)
+        obs_next = build(flat(o.gt, 1), flat(o.ubs, 1), flat(o.agent, 1), None, self.r_comm, static=True)
         return dict(obs=obs, obs_all=obs_all, obs_all_next=obs_next, h0=self.h0, h1=self.h1, acts=self.acts,
                     rews=self.rews, dones=self.dones)
 

@@ -148,7 +148,10 @@ class MultiAgentQLearner:
         self._gen.manual_seed(int(getattr(args, "seed", 0)) + 7919 * (dist.get_rank() if dist.is_initialized() else 0))
 
     def _build_agent(self):
-        return agent_REGISTRY["gnn"](self.obs_shape, self.n_actions, self.args)   # learner.py:62-67 ('gnn' arm)
+        """learner.py:64-67: flattened observations without communication -> 'rnn', everything else -> 'gnn'."""
+        if getattr(self.args, "o", None) == "mlp" and self.args.c is None:
+            return agent_REGISTRY["rnn"](self.obs_shape, self.n_actions, self.args)
+        return agent_REGISTRY["gnn"](self.obs_shape, self.n_actions, self.args)
 
     def init_hidden(self, batch_size: int = 1) -> th.Tensor:
         """[n_agents * batch_size, H] on the learner's device (learner.py:82-83).  The agent's one-row initial state (on

@@ -964,6 +964,93 @@ def linear_relu(x, W, b):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# First encoder layer of the flattened-observation agents, read straight from the padded observations (csrc/flat_obs.hip)
+# "1": the fused kernels wherever the shape is supported; "0": th.cat of the pieces + linear_relu; "auto" (default): the path that
+# measured faster (profiles/flat_obs_probe.txt, tools/flat_obs_probe.py) - the fused forward for no-grad calls (the rollout) of at most
+# FLAT_OBS_AUTO_MAX_ROWS rows and F <= FLAT_OBS_AUTO_MAX_F (16 384 rows, F = 31: 0.035 vs 0.042 ms), th.cat + linear_relu for everything
+# else (the time-batched training layer and 8 x 80: the FMA kernels run at 2-7x the vendor GEMM's time there)
+FLAT_OBS_FUSED = os.environ.get("UAVGNN_FLAT_OBS_FUSED", "auto")
+FLAT_OBS_AUTO_MAX_ROWS = 1 << 15
+FLAT_OBS_AUTO_MAX_F = 64
+
+
+def flat_obs_supported(parts, W, needs_grad=False) -> bool:
+    """parts: the (agent, gt, ubs) row views [rows, .] of a flattened-observation batch (graph.FlatObsBatch.parts).  Every piece needs
+    unit column stride and rows that do not overlap (an expanded or overlapping view takes the th.cat path).  needs_grad: the call
+    will be differentiated (the "auto" mode keeps those on th.cat + linear_relu)."""
+    F = sum(p.shape[1] for p in parts)
+    rows = parts[0].shape[0]
+    mode = str(FLAT_OBS_FUSED)
+    if mode == "0" or (mode != "1" and (needs_grad or rows > FLAT_OBS_AUTO_MAX_ROWS or F > FLAT_OBS_AUTO_MAX_F)):
+        return False
+    return bool(W.is_cuda and W.dtype == th.float32 and W.is_contiguous() and W.shape[1] == F
+                and all(p.is_cuda and p.dtype == th.float32 and p.dim() == 2 and p.shape[0] == rows
+                        and (p.stride(1) == 1 or p.shape[1] <= 1) and (rows <= 1 or p.stride(0) >= p.shape[1]) for p in parts)
+                and rows < 2 ** 31 and L.lib().uavgnn_flat_obs_supported(W.shape[0], F))
+
+
+def _flat_src(parts):
+    """(ptr, row stride, width) per piece, as the C ABI takes them (an empty piece passes NULL)."""
+    out = []
+    for p in parts:
+        out += [p.data_ptr() if p.shape[1] else None, p.stride(0) if p.shape[0] > 1 else p.shape[1], p.shape[1]]
+    return out
+
+
+class _FlatLinearReLU(th.autograd.Function):
+    """relu(flat(obs) W^T + b) where flat(obs) = [agent || gt || ubs] (graph.FLAT_OBS_ORDER) is never materialised: the forward
+    and the weight gradient read the three padded pieces through their row strides.  The observations carry no gradient; the
+    ReLU mask and the bias gradient come from the fused pass of csrc/colsum.hip, the weight gradient from row-chunk partials
+    [S, H_out, F] summed in a fixed order (deterministic)."""
+
+    @staticmethod
+    def forward(ctx, W, b, agent, gt, ubs):
+        parts = (agent, gt, ubs)
+        rows, H = agent.shape[0], W.shape[0]
+        y = th.empty((rows, H), dtype=th.float32, device=W.device)
+        with KERNEL_TIMER.span("flat_obs_fwd", (rows, H, W.shape[1])):
+            rc = L.lib().uavgnn_flat_obs_fwd(*_flat_src(parts), rows, W.data_ptr(), L.ptr(b), H, y.data_ptr(), y.stride(0), L.stream())
+        L.check(rc, "uavgnn_flat_obs_fwd")
+        ctx.has_bias = b is not None
+        ctx.save_for_backward(y, agent, gt, ubs)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        y, agent, gt, ubs = ctx.saved_tensors
+        parts = (agent, gt, ubs)
+        n, H = dy.shape
+        F = sum(p.shape[1] for p in parts)
+        lib = L.lib()
+        if dy.stride(1) != 1 or dy.stride(0) < H or dy.stride(0) % 4 or dy.data_ptr() % 16:
+            dy = dy.contiguous()
+        S = _row_blocks(n)
+        dym = th.empty((n, H), dtype=th.float32, device=dy.device)
+        db_part = th.zeros((S, H), dtype=th.float32, device=dy.device)
+        L.check(lib.uavgnn_relu_bwd_colsum(dy.data_ptr(), dy.stride(0), y.data_ptr(), y.stride(0), dym.data_ptr(), H, n, H,
+                                           db_part.data_ptr(), S, L.stream()), "uavgnn_relu_bwd_colsum")
+        dW = None
+        if ctx.needs_input_grad[0]:
+            Sw = lib.uavgnn_flat_obs_wgrad_chunks(n, H, F)
+            part = th.empty((Sw, H, F), dtype=th.float32, device=dy.device)
+            with KERNEL_TIMER.span("flat_obs_wgrad", (n, H, F)):
+                rc = lib.uavgnn_flat_obs_wgrad(dym.data_ptr(), dym.stride(0), H, *_flat_src(parts), n, part.data_ptr(), Sw, 0, L.stream())
+            L.check(rc, "uavgnn_flat_obs_wgrad")
+            dW = part.sum(0)
+        db = db_part.sum(0) if ctx.has_bias and ctx.needs_input_grad[1] else None
+        return dW, db, None, None, None
+
+
+def flat_linear_relu(parts, W, b):
+    """ReLU(Linear(W, b)) of the flattened observations whose pieces are ``parts`` (agent, gt, ubs row views): the fused kernel
+    where ``flat_obs_supported`` (FLAT_OBS_FUSED), else ``th.cat`` of the pieces + ``linear_relu``."""
+    needs_grad = th.is_grad_enabled() and (W.requires_grad or (b is not None and b.requires_grad))
+    if flat_obs_supported(parts, W, needs_grad):
+        return _FlatLinearReLU.apply(W, b, *parts)
+    return linear_relu(th.cat(parts, 1), W, b)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Fused recurrent step of the TarMAC agent: ONE autograd node per time step.
 
 class WeightGradSink:

@@ -17,7 +17,7 @@ from typing import Dict, Optional
 
 import torch as th
 
-from .graph import HeteroBatch, from_obs_dicts, from_padded_obs, batch as hb_batch
+from .graph import HeteroBatch, from_obs_dicts, from_padded_obs, from_padded_obs_flat, batch as hb_batch
 
 SCHEME = ("gt", "ubs", "agent", "d_u2u", "h", "state", "act", "rew", "done")
 
@@ -83,10 +83,30 @@ class SequenceReplay:
         assert self.size >= batch_size, "Insufficient samples for update."
         return th.randperm(self.size, generator=generator, device=self.device)[:batch_size]
 
-    def gather(self, idx: th.Tensor) -> Dict:
-        """Batch dict in the layout ``MultiAgentQLearner.loss`` consumes: obs = list of T+1 HeteroBatch of B envs."""
+    def gather(self, idx: th.Tensor, enc: str = "gnn") -> Dict:
+        """Batch dict in the layout ``MultiAgentQLearner.loss`` consumes: obs = list of T+1 HeteroBatch of B envs.
+        enc='mlp': flattened-observation batches (``from_padded_obs_flat``) over a time-major copy of the gathered observations, plus
+        ``obs_all`` / ``obs_all_next`` (row views of the same copy) for the learner's time-batched encoder."""
         B, T, n = idx.numel(), self.T, self.n
-        m = {k: v.index_select(0, idx) for k, v in self.mem.items()}
+        if enc not in ("gnn", "mlp"):
+            raise ValueError(f"enc must be 'gnn' or 'mlp', got {enc!r}")
+        if enc == "mlp" and self.device.type != "cuda":
+            raise ValueError("enc='mlp': flattened-observation batches are built on the GPU only (graph.from_padded_obs_flat)")
+        obs_keys = ("gt", "ubs", "agent", "d_u2u")
+        # enc='mlp': the observation fields are gathered TIME-MAJOR in the one copy of the gather ([T+1, B, ...]: index_select along the
+        # sequence dimension of the transposed ring), so every step and the time-batched rows are views the flat builder keeps as they are
+        m = {k: v.index_select(0, idx) for k, v in self.mem.items() if not (enc == "mlp" and k in obs_keys)}
+        out = dict(h0=m["h"][:, 0].reshape(B * n, -1), h1=m["h"][:, 1].reshape(B * n, -1),
+                   acts=m["act"].permute(1, 0, 2).reshape(T, B * n, 1), rews=m["rew"].permute(1, 0, 2).contiguous(),
+                   dones=m["done"].permute(1, 0, 2).contiguous(), states=m["state"].permute(1, 0, 2).contiguous())
+        if enc == "mlp":
+            tm = {k: self.mem[k].transpose(0, 1).index_select(1, idx) for k in obs_keys}              # [T+1, B, ...]
+            rows = lambda x, lo: x[lo:].reshape((-1,) + x.shape[2:])  # noqa: E731
+            out["obs"] = [from_padded_obs_flat(tm["gt"][t], tm["ubs"][t], tm["agent"][t], tm["d_u2u"][t], self.r_comm)
+                          for t in range(T + 1)]
+            out["obs_all"] = from_padded_obs_flat(rows(tm["gt"], 0), rows(tm["ubs"], 0), rows(tm["agent"], 0))
+            out["obs_all_next"] = from_padded_obs_flat(rows(tm["gt"], 1), rows(tm["ubs"], 1), rows(tm["agent"], 1))
+            return out
         obs = []
         for t in range(T + 1):
             if self.device.type == "cuda":
@@ -99,9 +119,8 @@ class SequenceReplay:
                               gt=m["gt"][b, t, i].numpy()) for i in range(n)]
                     gs.append(from_obs_dicts(o, m["d_u2u"][b, t].numpy(), self.r_comm))
                 obs.append(hb_batch(gs))
-        return dict(obs=obs, h0=m["h"][:, 0].reshape(B * n, -1), h1=m["h"][:, 1].reshape(B * n, -1),
-                    acts=m["act"].permute(1, 0, 2).reshape(T, B * n, 1), rews=m["rew"].permute(1, 0, 2).contiguous(),
-                    dones=m["done"].permute(1, 0, 2).contiguous(), states=m["state"].permute(1, 0, 2).contiguous())
+        out["obs"] = obs
+        return out
 
-    def sample(self, batch_size: int, generator: Optional[th.Generator] = None) -> Dict:
-        return self.gather(self.sample_indices(batch_size, generator))
+    def sample(self, batch_size: int, generator: Optional[th.Generator] = None, enc: str = "gnn") -> Dict:
+        return self.gather(self.sample_indices(batch_size, generator), enc)
