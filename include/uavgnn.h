@@ -263,8 +263,19 @@ int uavgnn_gemm_nt_h2(const float* X, int ldx, int K1, const float* X2, int ldx2
  * what uavgnn_row_absmax(X2) returns, bit for bit; a maximum is order-independent).  X2 must not be NULL. */
 int uavgnn_gemm_nt_h2_rm2(const float* X, int ldx, int K1, const float* X2, int ldx2, int M, int K, const float* rowmax, float* rowmax2_out,
                           const void* planes, int N, const float* bias, float* Y, int ldy, int epilogue, uavgnn_stream_t stream);
+/* uavgnn_gemm_nt_h2 on 128 x 64 output tiles, for products with few output columns (d c = d_gi W_ih[:, H:] of the recurrent step:
+ * [N, 768] x [768, 64], which the 256 x 128-tile kernel would run with half of every tile empty and the vendor's fp32 GEMM ran before):
+ * Y [M, N] = X [M, K] B^T.  One source, no bias / accumulate / ReLU; N % 64 == 0, K % 64 == 0, ldx % 4 == 0, ldy % 4 == 0, X / planes / Y 16-byte
+ * aligned (UAVGNN_EUNSUPPORTED otherwise).  rowmax and planes as for uavgnn_gemm_nt_h2; same arithmetic and accumulation order over K. */
+int uavgnn_gemm_nt_h2_n64(const float* X, int ldx, int M, int K, const float* rowmax, const void* planes, int N, float* Y, int ldy,
+                          uavgnn_stream_t stream);
 /* uavgnn_gru_gates_bwd_fused_sums / uavgnn_relu_bwd_colsum that ALSO write row_absmax [N] = max |.| over the rows of d_gi and d_gh /
- * of `out` (H = 256 / C = 256 only - one wavefront owns a row -, UAVGNN_EUNSUPPORTED otherwise; the second not in place). */
+ * of `out` (H = 256 / C = 256 only - one wavefront owns a row -, UAVGNN_EUNSUPPORTED otherwise; the second not in place).
+ * Packed mode of the gate entry: the r and z columns of d_gi and d_gh hold the same numbers, so a caller that passes
+ * d_gi == d_gh + H (in floats) gets ONE [N, 4H] buffer G = [dn_h | dr | dz | dn_i] based at d_gh (16-byte aligned), every gate
+ * gradient stored once: d_gi is the strided view G[:, H:4H] and d_gh, with its column blocks in the order n, r, z, the view G[:, :3H]
+ * (row stride 4H).  Under the plain meaning that pointer relation makes the two [N, 3H] outputs overlap, so no valid plain call has
+ * it.  col_sums, row_absmax and d_h are what the plain call writes, bit for bit. */
 int uavgnn_gru_gates_bwd_fused_sums_rowmax(const float* pre, const float* h, const float* d_hout, const float* dq, int n_out,
                                            const float* W_out, int N, int H, float* d_gi, float* d_gh, float* d_h, float* col_sums,
                                            float* row_absmax, uavgnn_stream_t stream);

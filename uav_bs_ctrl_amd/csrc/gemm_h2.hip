@@ -362,6 +362,139 @@ __global__ __launch_bounds__(NT) void gemm_nt_h2w8_kernel(const float* __restric
   }
 }
 
+// ---- 128 x 64 output tiles: products with 64 output columns (d c = d_gi W_ih[:, H:] of the recurrent step, [N, 768] x [768, 64]) --------
+// The 256 x 128-tile kernel above would run such a product on N / 256 workgroups with half of every tile empty.  Here eight wavefronts of
+// 32 x 32 (ONE v_mfma_f32_32x32x16_f16 tile each: 4 x 2 over the 128 x 64 tile) share the same staging layout (swizzle, planes) and the
+// same three-term arithmetic in the same order over K; N = 32 768 rows are 256 workgroups, one round of the CUs.  The kernel is bound by
+// streaming X once (9.7 GFLOP against 100 MB at the step's shape) with ONE workgroup per CU, so what counts is the bytes a CU keeps in
+// flight: a stage holds TWO 32-wide K slices (two sub-buffers in the layout above, one barrier per 64 columns of K) and the loads of
+// the next stage - 4 float4 of X and 2 chunks of B per thread, 48 KB per CU - are in flight across a whole stage of MFMAs.  (A register
+// ring that ran three 32-wide slices ahead was tried first: rolled, the compiler drains every outstanding load at the loop's back edge;
+// unrolled, it re-schedules the loads next to their uses - either way one slice, 24 KB, in flight: 35.5 us against the vendor's 33.3.)
+constexpr int BM6 = 128, BN6 = 64;
+constexpr int PA6 = BM6 * 4, PB6 = BN6 * 4;            // 16-byte chunks per split plane of the X / B tile of ONE 32-wide slice
+constexpr int SUB6 = 2 * PA6 + 2 * PB6;                // chunks per slice (24 KB)
+constexpr int BUF6 = 2 * SUB6;                         // chunks per stage: two slices (48 KB)
+
+__global__ __launch_bounds__(NT) void gemm_nt_h2n64_kernel(const float* __restrict__ X, int ldx, int M, int K,
+                                                           const unsigned short* __restrict__ Bp, int N, const float* __restrict__ winv,
+                                                           float* __restrict__ Y, int ldy, int col_blocks, const float* __restrict__ rm1) {
+  constexpr int LDT = BN6 + 4;
+  static_assert(BM6 * LDT * 4 <= 2 * BUF6 * 16, "the output tile fits the staging buffers");
+  __shared__ u32x4 smem[2 * BUF6];
+  __shared__ float sInv[BM6];       // 2^-e of the block's rows
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l32 = lane & 31, lh = lane >> 5, sw = swz32(l32);
+  const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
+  const int rb = blockIdx.x / col_blocks, cb = blockIdx.x - rb * col_blocks;
+  const int m0 = rb * BM6, n0 = cb * BN6;
+
+  f32x16 acc;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+
+  // X loader, per slice: float4 q = tid + 512 i (i < 2) -> row tid / 8 + 64 i, k = 4 (tid % 8); rows past M: clamped loads, masked stores
+  const int lr = tid >> 3, c4 = tid & 7;
+  unsigned xo[2];
+  float sca[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int row = min(m0 + lr + 64 * i, M - 1);
+    xo[i] = static_cast<unsigned>(row) * ldx + 4 * c4;
+    sca[i] = pow2f(scale_exp(rm1[row]));
+  }
+  if (tid < BM6) sInv[tid] = pow2f(-scale_exp(rm1[min(m0 + tid, M - 1)]));
+  const int sa_w = lr * 32 + (((c4 >> 1) ^ swz32(lr)) * 8) + (c4 & 1) * 4;   // f16 units inside an X plane
+  // B loader, per slice: ONE chunk per thread: plane tid / 256, row (tid / 4) % 64, chunk tid % 4 (N % 64 == 0: every row exists)
+  const int bpl = tid >> 8, brow = (tid >> 2) & 63, bc = tid & 3;
+  const unsigned bo = bpl * (static_cast<unsigned>(N) * K) + static_cast<unsigned>(n0 + brow) * K + 8 * bc;
+  const int sbw = 2 * PA6 + bpl * PB6 + brow * 4 + (bc ^ swz32(brow));
+  const int ns = K / (2 * BK);      // stages (K % 64 == 0)
+  float4 ra[2][2];                  // [slice of the stage][i]
+  u32x4 rw[2];
+  auto gload = [&](int t) {
+    const unsigned k0 = static_cast<unsigned>(min(t, ns - 1)) * (2 * BK);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) ra[s][i] = *reinterpret_cast<const float4*>(X + (xo[i] + k0 + s * BK));
+      rw[s] = *reinterpret_cast<const u32x4*>(Bp + (bo + k0 + s * BK));
+    }
+  };
+  auto lstore = [&](int buf) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      u32x4* sb = smem + buf * BUF6 + s * SUB6;
+      unsigned short* sa = reinterpret_cast<unsigned short*>(sb) + sa_w;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) stage4(sa + 64 * i * 32, PA6 * 8, ra[s][i], sca[i]);
+      sb[sbw] = rw[s];
+    }
+  };
+  struct Half {
+    f16x8 a[2], b[2];   // [plane]
+  };
+#define UAVGNN_N64_READ(F, buf, s, kh)                                                                     \
+  {                                                                                                        \
+    const u32x4* sb = smem + (buf) * BUF6 + (s) * SUB6;                                                    \
+    _Pragma("unroll") for (int pl = 0; pl < 2; ++pl) {                                                     \
+      F.a[pl] = as_frag(sb[pl * PA6 + (wm + l32) * 4 + ((2 * (kh) + lh) ^ sw)]);                           \
+      F.b[pl] = as_frag(sb[2 * PA6 + pl * PB6 + (wn + l32) * 4 + ((2 * (kh) + lh) ^ sw)]);                 \
+    }                                                                                                      \
+  }
+#define UAVGNN_N64_MFMA(F)                 \
+  {                                        \
+    acc = mfma32(F.a[0], F.b[1], acc);     \
+    acc = mfma32(F.a[1], F.b[0], acc);     \
+    acc = mfma32(F.a[0], F.b[0], acc);     \
+  }
+  gload(0);
+  lstore(0);
+  gload(1);
+  __syncthreads();
+  Half f0, f1, f2, f3;
+  UAVGNN_N64_READ(f0, 0, 0, 0)
+  for (int t = 0; t < ns; ++t) {
+    const int cur = t & 1;
+    UAVGNN_N64_READ(f1, cur, 0, 1)
+    lstore(cur ^ 1);                       // stage t + 1 (the tail re-stages the last stage: unconditional, straight-line)
+    gload(t + 2);
+    __builtin_amdgcn_sched_barrier(0);
+    UAVGNN_N64_MFMA(f0)
+    UAVGNN_N64_READ(f2, cur, 1, 0)
+    UAVGNN_N64_MFMA(f1)
+    UAVGNN_N64_READ(f3, cur, 1, 1)
+    UAVGNN_N64_MFMA(f2)
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();
+    UAVGNN_N64_READ(f0, cur ^ 1, 0, 0)
+    __builtin_amdgcn_sched_barrier(0);
+    UAVGNN_N64_MFMA(f3)
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#undef UAVGNN_N64_MFMA
+#undef UAVGNN_N64_READ
+  // un-scaling as above (2^-e_col, then 2^-e_row), then Y through an LDS tile: row-contiguous float4 stores
+  float* sT = reinterpret_cast<float*>(smem);             // [128][LDT] fp32
+  __syncthreads();                                       // the last fragment reads of the stale buffer
+  {
+    const float ci = winv[n0 + wn + l32];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int lrow = wm + 8 * (i >> 2) + 4 * lh + (i & 3);
+      sT[lrow * LDT + wn + l32] = acc[i] * ci * sInv[lrow];
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int idx = tid + NT * q, row = idx >> 4, cc = idx & 15;
+    if (m0 + row < M)
+      *reinterpret_cast<float4*>(Y + static_cast<size_t>(m0 + row) * ldy + n0 + 4 * cc) =
+          *reinterpret_cast<const float4*>(sT + row * LDT + 4 * cc);
+  }
+}
+
 }  // namespace
 }  // namespace uavgnn
 
@@ -443,4 +576,22 @@ extern "C" int uavgnn_gemm_nt_h2_rm2(const float* X, int ldx, int K1, const floa
                                      uavgnn_stream_t stream) {
   if (!rowmax2_out) return UAVGNN_EINVAL;
   return gemm_nt_h2_launch(X, ldx, K1, X2, ldx2, M, K, rowmax, nullptr, rowmax2_out, planes, N, bias, Y, ldy, epilogue, stream);
+}
+
+// Y [M, N] = X [M, K] B^T on 128 x 64 output tiles (products with few output columns: d c of the recurrent step).  One source, no bias,
+// no accumulation, no ReLU; N % 64 == 0, K % 64 == 0, ldy % 4 == 0, Y 16-byte aligned (rows leave through float4 stores); otherwise the operands and
+// the arithmetic of uavgnn_gemm_nt_h2 - the accumulation order over K is the same, so a column computed here equals that kernel's.
+extern "C" int uavgnn_gemm_nt_h2_n64(const float* X, int ldx, int M, int K, const float* rowmax, const void* planes, int N, float* Y,
+                                     int ldy, uavgnn_stream_t stream) {
+  if (M < 0 || !X || !planes || !Y || !rowmax || K <= 0 || N <= 0 || ldx < K || ldy < N) return UAVGNN_EINVAL;
+  if (M == 0) return 0;
+  if (!uavgnn_gemm_h2_supported(M, N, K) || (N % BN6) || (K % (2 * BK)) || (ldx & 3) || (ldy & 3) || static_cast<long long>(M) * ldx >= (1LL << 31) ||
+      ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(planes) | reinterpret_cast<uintptr_t>(Y)) & 15))
+    return UAVGNN_EUNSUPPORTED;
+  const unsigned short* bp = static_cast<const unsigned short*>(planes);
+  const float* winv = reinterpret_cast<const float*>(bp + 2LL * N * K);
+  const int col_blocks = N / BN6, row_blocks = (M + BM6 - 1) / BM6;
+  hipLaunchKernelGGL(gemm_nt_h2n64_kernel, dim3(row_blocks * col_blocks), dim3(NT), 0, static_cast<hipStream_t>(stream), X, ldx, M, K, bp,
+                     N, winv, Y, ldy, col_blocks, rowmax);
+  return launch_status();
 }

@@ -182,7 +182,9 @@ __global__ __launch_bounds__(256, 2) void gru_cell_fwd_kernel(
 // block that share them are added in a fixed order through LDS: deterministic.
 // RM (H = 256 only: the 64 lanes of a wavefront own ONE row): row_absmax[row] = max |.| over the row of d_gi and of d_gh - the row
 // scales of the f16x2 products d x = [d_gi || d_proj] W and d h += d_gh W_hh behind this kernel (csrc/gemm_h2.hip).
-template <bool HEAD, bool SUMS, bool RM = false>
+// PACK: ONE [N, 4H] buffer G = [dn_h | dr | dz | dn_i] at d_gh instead of the two [N, 3H] ones, whose r / z columns hold the same
+// numbers: d_gi = G[:, H:4H] and (columns in the order n, r, z) d_gh = G[:, :3H] are strided views of it; d_gi is not touched.
+template <bool HEAD, bool SUMS, bool RM = false, bool PACK = false>
 __global__ __launch_bounds__(256) void gru_gates_bwd_fused_kernel(const float* __restrict__ pre, const float* __restrict__ h,
                                                                   const float* __restrict__ d_hout, long long total, int H,
                                                                   float* __restrict__ d_gi, float* __restrict__ d_gh,
@@ -234,14 +236,22 @@ __global__ __launch_bounds__(256) void gru_gates_bwd_fused_kernel(const float* _
         cs[12 + t] += dnh[t];
       }
     }
-    float* gi = d_gi + row * 3 * H + col;
-    float* gh = d_gh + row * 3 * H + col;
-    *reinterpret_cast<float4*>(gi) = make_float4(dr[0], dr[1], dr[2], dr[3]);
-    *reinterpret_cast<float4*>(gi + H) = make_float4(dz[0], dz[1], dz[2], dz[3]);
-    *reinterpret_cast<float4*>(gi + 2 * H) = make_float4(dni[0], dni[1], dni[2], dni[3]);
-    *reinterpret_cast<float4*>(gh) = make_float4(dr[0], dr[1], dr[2], dr[3]);
-    *reinterpret_cast<float4*>(gh + H) = make_float4(dz[0], dz[1], dz[2], dz[3]);
-    *reinterpret_cast<float4*>(gh + 2 * H) = make_float4(dnh[0], dnh[1], dnh[2], dnh[3]);
+    if constexpr (PACK) {
+      float* g4 = d_gh + row * 4 * H + col;
+      *reinterpret_cast<float4*>(g4) = make_float4(dnh[0], dnh[1], dnh[2], dnh[3]);
+      *reinterpret_cast<float4*>(g4 + H) = make_float4(dr[0], dr[1], dr[2], dr[3]);
+      *reinterpret_cast<float4*>(g4 + 2 * H) = make_float4(dz[0], dz[1], dz[2], dz[3]);
+      *reinterpret_cast<float4*>(g4 + 3 * H) = make_float4(dni[0], dni[1], dni[2], dni[3]);
+    } else {
+      float* gi = d_gi + row * 3 * H + col;
+      float* gh = d_gh + row * 3 * H + col;
+      *reinterpret_cast<float4*>(gi) = make_float4(dr[0], dr[1], dr[2], dr[3]);
+      *reinterpret_cast<float4*>(gi + H) = make_float4(dz[0], dz[1], dz[2], dz[3]);
+      *reinterpret_cast<float4*>(gi + 2 * H) = make_float4(dni[0], dni[1], dni[2], dni[3]);
+      *reinterpret_cast<float4*>(gh) = make_float4(dr[0], dr[1], dr[2], dr[3]);
+      *reinterpret_cast<float4*>(gh + H) = make_float4(dz[0], dz[1], dz[2], dz[3]);
+      *reinterpret_cast<float4*>(gh + 2 * H) = make_float4(dnh[0], dnh[1], dnh[2], dnh[3]);
+    }
     *reinterpret_cast<float4*>(d_h + row * H + col) = make_float4(dh[0], dh[1], dh[2], dh[3]);
     if constexpr (RM) {
       float m = 0.f;
@@ -354,7 +364,9 @@ extern "C" int uavgnn_gru_gates_bwd_fused_sums(const float* pre, const float* h,
 }
 
 // ... that ALSO writes row_absmax [N] = max |.| over the rows of d_gi and d_gh (H = 256: one wavefront per row; UAVGNN_EUNSUPPORTED
-// otherwise): the row scales of the f16x2 input-gradient products behind it (uavgnn_gemm_nt_h2)
+// otherwise): the row scales of the f16x2 input-gradient products behind it (uavgnn_gemm_nt_h2).
+// Packed mode: d_gi == d_gh + H (a relation under which the two [N, 3H] outputs of the plain call would overlap, so no plain call has
+// it) selects ONE [N, 4H] output G = [dn_h | dr | dz | dn_i] based at d_gh - every gate gradient stored once; see include/uavgnn.h.
 extern "C" int uavgnn_gru_gates_bwd_fused_sums_rowmax(const float* pre, const float* h, const float* d_hout, const float* dq, int n_out,
                                                       const float* W_out, int N, int H, float* d_gi, float* d_gh, float* d_h,
                                                       float* col_sums, float* row_absmax, uavgnn_stream_t stream) {
@@ -367,6 +379,16 @@ extern "C" int uavgnn_gru_gates_bwd_fused_sums_rowmax(const float* pre, const fl
     return UAVGNN_EUNSUPPORTED;
   const long long total = static_cast<long long>(N) * (H / 4);
   const dim3 grid(capped_grid(total, 256)), block(256);
+  if (d_gi == d_gh + H) {
+    if ((reinterpret_cast<uintptr_t>(d_gh) & 15)) return UAVGNN_EUNSUPPORTED;
+    if (dq != nullptr)
+      hipLaunchKernelGGL((gru_gates_bwd_fused_kernel<true, true, true, true>), grid, block, 0, static_cast<hipStream_t>(stream), pre, h, d_hout,
+                         total, H, nullptr, d_gh, d_h, dq, n_out, W_out, col_sums, row_absmax);
+    else
+      hipLaunchKernelGGL((gru_gates_bwd_fused_kernel<false, true, true, true>), grid, block, 0, static_cast<hipStream_t>(stream), pre, h,
+                         d_hout, total, H, nullptr, d_gh, d_h, nullptr, 0, nullptr, col_sums, row_absmax);
+    return launch_status();
+  }
   if (dq != nullptr)
     hipLaunchKernelGGL((gru_gates_bwd_fused_kernel<true, true, true>), grid, block, 0, static_cast<hipStream_t>(stream), pre, h, d_hout, total,
                        H, d_gi, d_gh, d_h, dq, n_out, W_out, col_sums, row_absmax);

@@ -785,6 +785,42 @@ def gemm_h2(a, W, rowmax, transpose_w=False, bias=None, out=None, accumulate=Fal
     return out
 
 
+# The gate gradients of a staged BPTT step as ONE [N, 4H] buffer G = [dn_h | dr | dz | dn_i] (packed mode of
+# uavgnn_gru_gates_bwd_fused_sums_rowmax) instead of d_gi / d_gh [N, 3H] each, whose r / z columns hold the same numbers: a third of the
+# kernel's gate-gradient writes and of the stage buffers; the consumers read strided views.  A/B switch
+G4 = os.environ.get("UAVGNN_G4", "1") != "0"
+# d c = d_gi W_ih[:, H:] of the recurrent step on the f16x2 arithmetic, 128 x 64 output tiles (csrc/gemm_h2.hip); 0: vendor fp32 GEMM (A/B)
+DC_H2 = os.environ.get("UAVGNN_DC_H2", "1") != "0"
+GEMM_H2_N64_MIN_GRID = 128   # fewer 128 x 64 tiles than this (half the CUs): the vendor GEMM
+
+
+def gemm_h2_n64_supported(a, n_out, k) -> bool:
+    """The 128 x 64-tile f16x2 kernel covers y = a B^T with n_out % 64 == 0 on a grid that fills at least half the chip."""
+    return bool(DC_H2 and GEMM_H2 and a.is_cuda and a.dtype == th.float32 and a.dim() == 2 and a.stride(1) == 1 and a.shape[1] == k
+                and a.stride(0) % 4 == 0 and a.data_ptr() % 16 == 0 and n_out % 64 == 0 and k % 64 == 0 and a.shape[0] * a.stride(0) < 2 ** 31
+                and L.lib().uavgnn_gemm_h2_supported(a.shape[0], n_out, k)
+                and ((a.shape[0] + 127) // 128) * (n_out // 64) >= GEMM_H2_N64_MIN_GRID)
+
+
+def gemm_h2_n64(a, W, rowmax, out=None):
+    """out = a @ W (W [k, n_out], a view with unit inner stride) on the 128 x 64-tile f16x2 kernel.  rowmax: per row an upper bound of
+    max |.| over the row of `a`, from its producer.  Caller checks gemm_h2_n64_supported()."""
+    lib = L.lib()
+    M, K = a.shape
+    R, n_out = W.shape
+    assert R == K and W.stride(1) == 1
+    if out is None:
+        out = th.empty((M, n_out), dtype=th.float32, device=a.device)
+    with KERNEL_TIMER.span("gemm_h2_n64", (M, n_out, K)):
+        planes = _cached_planes(("h2mat", W.data_ptr(), W._version, W.stride(0), R, n_out, True), lib.uavgnn_split_h2_bytes(n_out, K),
+                                a.device, lambda p: L.check(lib.uavgnn_split_h2(W.data_ptr(), W.stride(0), R, n_out, 1, p.data_ptr(),
+                                                                                 L.stream()), "uavgnn_split_h2"), keep=(W,))
+        rc = lib.uavgnn_gemm_nt_h2_n64(a.data_ptr(), a.stride(0), M, K, rowmax.data_ptr(), planes.data_ptr(), n_out, out.data_ptr(),
+                                       out.stride(0), L.stream())
+    L.check(rc, "uavgnn_gemm_nt_h2_n64")
+    return out
+
+
 GEMM_TN_X3 = os.environ.get("UAVGNN_GEMM_TN_X3", "1") != "0"   # weight gradients on the bf16 matrix cores (csrc/gemm_tn_x3.hip)
 # Measured against the vendor's batched split-K fp32 GEMM (tools/gemm_tn_probe.py, profiles/r03_gemm_tn_probe.txt): BOTH operands
 # have to be split and transposed inside the kernel, which bounds it at 95-108 TFLOP/s fp32-equivalent = the vendor's 106-108
@@ -1149,11 +1185,22 @@ class WeightGradSink:
             return
         T1, N = seq.T1, seq.N
         full = sorted(seq.bwd_steps) == list(range(T1)) and seq.t_fwd == T1
+        if full and 0 < len(seq.g4_steps) < T1:
+            full = False         # packed and plain gate-gradient slots in one sequence (never from one caller): reduce per step
         spans = [(0, T1)] if full else [(t, t + 1) for t in sorted(seq.bwd_steps)]
         split, ids, H = seq.split, seq.ids, seq.H
         for (t0, t1) in spans:
             rows = lambda name, lo=0: seq.bufs[name][t0 + lo:t1 + lo].reshape((t1 - t0) * N, -1)   # noqa: E731
-            d_proj, d_gi, d_gh = rows("d_proj"), rows("d_gi"), rows("d_gh")
+            d_proj = rows("d_proj")
+            g4 = t0 in seq.g4_steps
+            if g4:
+                # G = [dn_h | dr | dz | dn_i]: d_gi is a view; d_gh comes with its column blocks in the order n, r, z, so dW_hh is
+                # accumulated with its row blocks in that order (a slot of its own) and put back in order once, at flush
+                d_gi, d_gh = rows("g4")[:, H:], rows("g4")[:, :3 * H]
+                whh_key, whh_flush = "W_hh_nrz", lambda g: split("W_hh", th.cat((g[H:], g[:H]), 0), 0)
+            else:
+                d_gi, d_gh = rows("d_gi"), rows("d_gh")
+                whh_key, whh_flush = "W_hh", lambda g: split("W_hh", g, 0)
             dq = seq.dq_rows(t0, t1)
             x = seq.x_all[t0 * N:t1 * N]
             h, h2, inp = rows("h"), rows("h", 1), rows("inp")
@@ -1181,10 +1228,10 @@ class WeightGradSink:
                 # bits (absolute error <= 2^-39 of the bound per element, averaged down over 10^6 rows: DESIGN.md section 5)
                 bx, by = _max_two_stage(seq.bufs["rowmax"][:T1]), _max_two_stage(seq.bufs["rm_g"][:T1])
                 self.weight_h2(("W_ih", ids["W_ih"]), d_gi, inp, by, bx, lambda g: split("W_ih", g, 0))
-                self.weight_h2(("W_hh", ids["W_hh"]), d_gh, h, by, bx, lambda g: split("W_hh", g, 0))
+                self.weight_h2((whh_key, ids["W_hh"]), d_gh, h, by, bx, whh_flush)
             else:
                 self.weight(("W_ih", ids["W_ih"]), d_gi, inp, lambda g: split("W_ih", g, 0), tn)
-                self.weight(("W_hh", ids["W_hh"]), d_gh, h, lambda g: split("W_hh", g, 0), tn)
+                self.weight((whh_key, ids["W_hh"]), d_gh, h, whh_flush, tn)
             if all(t in seq.gsum_steps for t in range(t0, t1)):
                 # the gate kernels of these steps left per-workgroup column sums d_r | d_z | d_n (input) | d_n (hidden): [., 4H]
                 gs = seq.bufs["gsum"][t0:t1]
@@ -1193,7 +1240,7 @@ class WeightGradSink:
                 self.bias(("b_hh_n", ids["W_hh"]), gs[:, 3 * H:], lambda g: split("b_hh", g, 2 * H))
             else:
                 self.bias(("b_ih", ids["W_ih"]), d_gi, lambda g: split("b_ih", g, 0))
-                self.bias(("b_hh_n", ids["W_hh"]), d_gh[:, 2 * H:], lambda g: split("b_hh", g, 2 * H))
+                self.bias(("b_hh_n", ids["W_hh"]), d_gh[:, :H] if g4 else d_gh[:, 2 * H:], lambda g: split("b_hh", g, 2 * H))
             self.weight(("W_out", ids["W_out"]), dq, h2, lambda g: split("W_out", g, 0), tn)
             self.bias(("b_out", ids["W_out"]), dq, lambda g: split("b_out", g, 0))
 
@@ -1218,6 +1265,7 @@ class _SequenceStage:
         self.gsum_steps = set()          # steps whose gate kernel wrote its column-sum partials ("gsum" slots)
         self.rowmax_steps = set()        # steps whose message kernel left the row maxima of [x || c || h] ("rowmax" slots)
         self.rm_g_steps = set()          # steps whose gate kernel left the row maxima of d_gi / d_gh ("rm_g" slots)
+        self.g4_steps = set()            # steps whose gate kernel wrote ONE packed [N, 4H] buffer ("g4" slots) instead of "d_gi" / "d_gh"
         self.rm_p_steps = set()          # steps whose backward took the row maxima of d_proj ("rm_p" slots)
         self.dq_steps = {}               # step -> the gradient of the step's Q values as autograd handed it over
         self.split = self.ids = self.H = None
@@ -1484,7 +1532,7 @@ class _TarmacStep(th.autograd.Function):
         if not ctx.have_pre:    # gi would be the [N, H] placeholder: reading 4H floats per row from it is out of bounds
             raise L.UavGnnError("tarmac_step: backward through a forward that saved no pre-activations (train=False)")
         sink = GRAD_SINK
-        rm_g = None
+        rm_g = g4 = None
         dq = L.f32c(dq) if dq is not None else th.zeros((N, W_out.shape[0]), dtype=th.float32, device=x.device)
         # d h' = d_hout + dq W_out inside the gate kernel when the cell ran fused (its pre-activation sets are what that kernel reads)
         head = None
@@ -1518,11 +1566,21 @@ class _TarmacStep(th.autograd.Function):
                 sums = seq.slot("gsum", t, 4 * H, rows=G)
                 seq.gsum_steps.add(t)
             rm_g = None
-            if (sums is not None and H == 256 and W_hh.stride(1) == 1 and gemm_h2_supported(seq.slot("d_gh", t, 3 * H), H, 3 * H)):
-                rm_g = seq.slot("rm_g", t, 1).view(N)      # row maxima of d_gi / d_gh for the f16x2 products below (and, over the whole
-                seq.rm_g_steps.add(t)                      # sequence, for the weight gradients)
-            d_gi, d_gh, dh = _gru_gates_bwd_from_pre(gi, h, dh2_tot, seq.slot("d_gi", t, 3 * H), seq.slot("d_gh", t, 3 * H),
-                                                     head=head, sums=sums, rowmax=rm_g)
+            if sums is not None and H == 256 and W_hh.stride(1) == 1:
+                if G4 and gemm_h2_supported(seq.slot("g4", t, 4 * H)[:, H:], H, 3 * H):
+                    g4 = seq.slot("g4", t, 4 * H)          # ONE buffer [dn_h | dr | dz | dn_i]: the r / z columns are stored once
+                    seq.g4_steps.add(t)
+                if g4 is not None or gemm_h2_supported(seq.slot("d_gh", t, 3 * H), H, 3 * H):
+                    rm_g = seq.slot("rm_g", t, 1).view(N)  # row maxima of d_gi / d_gh for the f16x2 products below (and, over the whole
+                    seq.rm_g_steps.add(t)                  # sequence, for the weight gradients)
+            if g4 is not None:
+                # packed mode of the gate entry: d_gi == d_gh + H.  d_gi = G[:, H:] in its natural order; `d_gh` is NOT the plain
+                # operand (its column blocks come in the order n, r, z): d h below takes it as two sources
+                d_gi, _, dh = _gru_gates_bwd_from_pre(gi, h, dh2_tot, g4[:, H:], g4[:, :3 * H], head=head, sums=sums, rowmax=rm_g)
+                d_gh = None
+            else:
+                d_gi, d_gh, dh = _gru_gates_bwd_from_pre(gi, h, dh2_tot, seq.slot("d_gi", t, 3 * H), seq.slot("d_gh", t, 3 * H),
+                                                         head=head, sums=sums, rowmax=rm_g)
         elif ctx.fused_gru:
             d_gi, d_gh, dh = _gru_gates_bwd_from_pre(gi, h, dh2_tot, head=head)      # gi holds the saved pre-activation sets
         else:
@@ -1547,12 +1605,20 @@ class _TarmacStep(th.autograd.Function):
             dx_cat = Wp.stride(1) == 1 and gemm_x3_cat_supported(d_gi, d_proj, H)
             if not dx_cat:
                 _mm_nn(d_gi, W_ih[:, :H], out=dx)
-            d_c = th.mm(d_gi, W_ih[:, H:])                                 # [N, M]
+            if rm_g is not None and M == 64 and gemm_h2_n64_supported(d_gi, M, 3 * H):
+                d_c = gemm_h2_n64(d_gi, W_ih[:, H:], rm_g)                 # [N, M], f16x2 on 128 x 64 tiles
+            else:
+                d_c = th.mm(d_gi, W_ih[:, H:])                             # [N, M]
             d_c_ptr, d_c_ld = d_c.data_ptr(), M
         else:
             d_inp = _mm_nn(d_gi, W_ih)
             d_c_ptr, d_c_ld = d_inp.data_ptr() + 4 * H, H + M
-        _mm_nn(d_gh, W_hh, out=dh, accumulate=True, rowmax=rm_g)
+        if g4 is not None:
+            # d h += d_gh W_hh over K in the order r, z, n as ever: [G[:, H:3H] || G[:, :H]] [W_hh[:2H]; W_hh[2H:]] (the stacked weight IS
+            # W_hh: the same planes and scales)
+            gemm_h2(g4[:, H:3 * H], W_hh[:2 * H], rm_g, True, out=dh, accumulate=True, a2=g4[:, :H], W2=W_hh[2 * H:])
+        else:
+            _mm_nn(d_gh, W_hh, out=dh, accumulate=True, rowmax=rm_g)
         if sink is not None:
             sink.owned.clear()
             sink.owned[dh.data_ptr()] = dh
