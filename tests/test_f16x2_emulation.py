@@ -1,4 +1,5 @@
-"""The arithmetic of csrc/gemm_tn_h2.hip (the f16x2 weight gradient dW = dY^T X) restated in NumPy (CPU, no GPU needed), and the
+"""The f16x2 arithmetic of csrc/f16x2.h (`scale_exp`, `split_pair`), as csrc/gemm_tn_h2.hip uses it for the weight gradient
+dW = dY^T X, restated in NumPy (CPU, no GPU needed), and the
 error floor of its column bounds.  The kernel splits every element v of a column whose bound is B into two f16 terms at a power-of-two
 scale s with B s in [2^14, 2^15) (`scale_exp`): hi = f16(v s), lo = f16(v s - hi), f16 subnormals kept; it forms hi hi + hi lo + lo hi
 on the matrix cores (lo lo dropped) and accumulates in fp32.  The learner passes ONE bound per operand (WeightGradSink.end_sequence:
@@ -30,7 +31,7 @@ LADDER = (17, 24, 30, 40)       # columns 2^-k below the operand's global bound
 
 
 def scale_exp(amax):
-    """csrc/gemm_tn_h2.hip scale_exp: 2^se * amax in [2^14, 2^15), clamped to the normal range (amax: fp32)."""
+    """csrc/f16x2.h scale_exp: 2^se * amax in [2^14, 2^15), clamped to the normal range (amax: fp32)."""
     e = ((np.asarray(amax, dtype=np.float32).view(np.uint32) >> 23) & 0xFF).astype(np.int64)
     return np.clip(14 - (e - 127), -126, 126)
 

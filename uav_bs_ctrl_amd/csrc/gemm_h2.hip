@@ -9,53 +9,23 @@
 //   * uavgnn_row_absmax                        anything else, as a pass of its own (d_proj: 96 columns).
 // Up to two bounds per row (two producers of a two-source operand); the row's scale comes from their maximum.
 //
-// Arithmetic, error and non-finite behaviour: csrc/gru_h2.hip's header.  B (the weight, [N, K] or its transpose) is split per OUTPUT
-// row by uavgnn_split_h2: f16 planes [2][N][K] + 2^-e per row.
+// Arithmetic, error and non-finite behaviour: csrc/gru_h2.hip's header (the shared device helpers: csrc/f16x2.h).  B (the weight,
+// [N, K] or its transpose) is split per OUTPUT row by uavgnn_split_h2: f16 planes [2][N][K] + 2^-e per row.
 //
 // Kernel: gemm_x3.hip's eight-wave kernel (256 x 128 output tile, waves of 64 x 64 = 2 x 2 tiles of v_mfma_f32_32x32x16_f16, LDS
 // double-buffered with ONE barrier per 32-wide K slice, two-source X loader) with two planes: 48 KB per LDS stage instead of 72, 24
 // MFMAs per slice and wavefront instead of 48.
 #include "common.h"
+#include "f16x2.h"
 
 namespace uavgnn {
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+using namespace h2;
 
 constexpr int BN = 128, BK = 32, BM8 = 256, NT = 512;
 constexpr int PA = BM8 * 4, PB = BN * 4;               // 16-byte chunks per split plane of the X / B tile
 constexpr int BUF = 2 * PA + 2 * PB;                   // chunks per buffer (48 KB)
-
-__device__ __forceinline__ int swz32(int row) { return (row >> 2) & 3; }
-__device__ __forceinline__ f16x8 as_frag(u32x4 v) { return __builtin_bit_cast(f16x8, v); }
-__device__ __forceinline__ f32x16 mfma32(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ int scale_exp(float amax) {   // 2^se * amax in [2^14, 2^15); clamped to the normal range
-  const int e = static_cast<int>((__float_as_uint(amax) >> 23) & 0xffu);
-  return max(-126, min(126, 14 - (e - 127)));
-}
-__device__ __forceinline__ float pow2f(int e) { return __uint_as_float(static_cast<unsigned>(e + 127) << 23); }
-
-struct Split2 {
-  unsigned hi, lo;
-};
-__device__ __forceinline__ Split2 split_pair(float x, float y) {
-  Split2 s;
-  const f16x2 h = __builtin_convertvector(f32x2{x, y}, f16x2);
-  s.hi = __builtin_bit_cast(unsigned, h);
-  const f32x2 r = f32x2{x, y} - __builtin_convertvector(h, f32x2);
-  s.lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
-  return s;
-}
-__device__ __forceinline__ void stage4(unsigned short* p, int plane_stride, float4 v, float s) {
-  const Split2 a = split_pair(v.x * s, v.y * s), b = split_pair(v.z * s, v.w * s);
-  *reinterpret_cast<u32x2*>(p) = u32x2{a.hi, b.hi};
-  *reinterpret_cast<u32x2*>(p + plane_stride) = u32x2{a.lo, b.lo};
-}
 
 // W [R, C] (row stride ld) -> planes [2][R][C] (transpose: [2][C][R]) + winv[rows of the output] = 2^-e: one workgroup per output row
 __global__ __launch_bounds__(256) void split_h2_kernel(const float* __restrict__ W, int ld, int R, int C, int transpose,

@@ -1,4 +1,4 @@
-// Weight gradients of the dense layers on the f16 matrix cores with exactly scaled two-term splits ("f16x2", csrc/gru_h2.hip):
+// Weight gradients of the dense layers on the f16 matrix cores with exactly scaled two-term splits ("f16x2", csrc/gru_h2.hip; helpers: csrc/f16x2.h):
 //   P[s][Mo, Ko] (+)= dY[rows_s, :Mo]^T X[rows_s, :Ko],   fp32 in / out / accumulate, three f16 x f16 MFMA products per fp32 product.
 // Replaces autograd's dW = dy^T x of the nn.GRUCell / nn.Linear layers of /root/reference/algos/madrqn/agents/gnn_agents.py:246 (f_udt),
 // :99 (f_aggr) under loss.backward() (algos/madrqn/learner.py:157) over the time-batched rows of a BPTT sequence (1.67 M at C3), which
@@ -19,17 +19,15 @@
 // cut into S chunks, all tiles of a chunk on one XCD (a row slice is fetched from HBM once per chunk), one partial product per chunk (the
 // caller sums the S partials in a fixed order: deterministic).
 #include "common.h"
+#include "f16x2.h"
 
 namespace uavgnn {
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+using namespace h2;
+
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int TI = 256, TJ = 128, BK = 32, NT = 512;
 #ifndef GEMM_TN_H2_SUBE
@@ -39,30 +37,6 @@ constexpr int SUBE = GEMM_TN_H2_SUBE;
 constexpr int PA = (TI / 16) * SUBE, PB = (TJ / 16) * SUBE;   // elements per plane of the dY / X tile
 constexpr int BUF = 2 * PA + 2 * PB;                           // elements per buffer
 
-__device__ __forceinline__ f32x16 mfma32(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ int scale_exp(float amax) {   // 2^se * amax in [2^14, 2^15); clamped to the normal range
-  const int e = static_cast<int>((__float_as_uint(amax) >> 23) & 0xffu);
-  return max(-126, min(126, 14 - (e - 127)));
-}
-__device__ __forceinline__ float pow2f(int e) { return __uint_as_float(static_cast<unsigned>(e + 127) << 23); }
-
-struct Split2 {
-  unsigned hi, lo;
-};
-__device__ __forceinline__ Split2 split_pair(float x, float y) {
-  Split2 s;
-  const f16x2 h = __builtin_convertvector(f32x2{x, y}, f16x2);
-  s.hi = __builtin_bit_cast(unsigned, h);
-  const f32x2 r = f32x2{x, y} - __builtin_convertvector(h, f32x2);
-  s.lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
-  return s;
-}
-// four consecutive columns of one row, each with its own column scale -> one 8-byte group per plane
-__device__ __forceinline__ void stage4(unsigned short* p, int plane_stride, float4 v, float4 s) {
-  const Split2 a = split_pair(v.x * s.x, v.y * s.y), b = split_pair(v.z * s.z, v.w * s.w);
-  *reinterpret_cast<u32x2*>(p) = u32x2{a.hi, b.hi};
-  *reinterpret_cast<u32x2*>(p + plane_stride) = u32x2{a.lo, b.lo};
-}
 // one MFMA operand fragment (8 consecutive k of the lane's column) from a [k][column] sub-tile image: two transposing reads
 __device__ __forceinline__ f16x8 tr_frag(const unsigned short* p) {
   typedef __attribute__((address_space(3))) s16x4 lds_s16x4;

@@ -34,52 +34,17 @@
 #include <type_traits>
 
 #include "common.h"
+#include "f16x2.h"
+#include "gru_gates.h"
 
 namespace uavgnn {
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+using namespace h2;
 
 constexpr int BM = 128, BK = 32, BJ = 64, NT = 512, ST = 68;
 constexpr int PA = BM * 4, PB = 3 * BJ * 4;            // 16-byte chunks per split plane of the A / B tile
 constexpr int BUF = 2 * PA + 2 * PB;                   // chunks per buffer (40 KB)
-
-__device__ __forceinline__ float sigmoidf_(float x) { return __frcp_rn(1.f + __expf(-x)); }
-__device__ __forceinline__ float tanhf_(float x) { return 1.f - 2.f * __frcp_rn(1.f + __expf(2.f * x)); }
-__device__ __forceinline__ int swz32(int row) { return (row >> 2) & 3; }
-__device__ __forceinline__ f16x8 as_frag(u32x4 v) { return __builtin_bit_cast(f16x8, v); }
-__device__ __forceinline__ f32x16 mfma32(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-
-// scale exponent of a row whose largest magnitude is `amax`: 2^se * amax lies in [2^14, 2^15) (se clamped to the normal range)
-__device__ __forceinline__ int scale_exp(float amax) {
-  const int e = static_cast<int>((__float_as_uint(amax) >> 23) & 0xffu);      // biased exponent; 255: Inf / NaN, 0: zero / subnormal
-  return max(-126, min(126, 14 - (e - 127)));
-}
-__device__ __forceinline__ float pow2f(int e) { return __uint_as_float(static_cast<unsigned>(e + 127) << 23); }
-
-struct Split2 {
-  unsigned hi, lo;   // two packed f16 each: low half = first element
-};
-// (x, y) already scaled -> hi + lo (round to nearest even both times; x - hi is exact in fp32)
-__device__ __forceinline__ Split2 split_pair(float x, float y) {
-  Split2 s;
-  const f16x2 h = __builtin_convertvector(f32x2{x, y}, f16x2);
-  s.hi = __builtin_bit_cast(unsigned, h);
-  const f32x2 r = f32x2{x, y} - __builtin_convertvector(h, f32x2);
-  s.lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
-  return s;
-}
-// four consecutive k of one row (one 16-byte global load) scaled by `s` -> one 8-byte group per plane
-__device__ __forceinline__ void stage4(unsigned short* p, int plane_stride, float4 v, float s) {
-  const Split2 a = split_pair(v.x * s, v.y * s), b = split_pair(v.z * s, v.w * s);
-  *reinterpret_cast<u32x2*>(p) = u32x2{a.hi, b.hi};
-  *reinterpret_cast<u32x2*>(p + plane_stride) = u32x2{a.lo, b.lo};
-}
 
 // [W_ih | W_hh] -> f16 planes [2][3H][K_in] and [2][3H][H] + winv[3H] = 2^-e_row: one workgroup per output row (both matrices share
 // the row's scale: the r and z accumulators sum both contractions)
@@ -348,8 +313,8 @@ __global__ __launch_bounds__(NT) void gru_cell_fwd_h2_kernel(
     // two exact power-of-two factors (their product alone may leave the fp32 range), then the bias: one rounding, as before
     const float pr = acc[0][i] * ri * ci_r + b_r, pz = acc[1][i] * ri * ci_z + b_z;
     const float gin = acc[2][i] * ri * ci_n + b_in, ghn = acc[3][i] * ri * ci_n + b_hn;
-    const float rr = sigmoidf_(pr), zz = sigmoidf_(pz);
-    const float nn = tanhf_(fmaf(rr, ghn, gin));
+    const float rr = fast_sigmoid(pr), zz = fast_sigmoid(pz);
+    const float nn = fast_tanh(fmaf(rr, ghn, gin));
     float* hp = sH + lrow * ST + wc + l32;
     *hp = fmaf(zz, *hp - nn, nn);                          // every element of the tile has exactly one owner lane
     if (SAVE && row < N) {

@@ -31,17 +31,13 @@
 
 #include "bf16x3.h"
 #include "common.h"
+#include "gru_gates.h"
 
 namespace uavgnn {
 namespace {
 
 using namespace x3;
 constexpr int BM = 128, BK = 32;
-
-// gate non-linearities on the hardware transcendentals (v_exp_f32, v_rcp_f32: 1 ulp each): absolute error <= 2e-7, far inside
-// the 1e-5 parity tolerance; tanh as 1 - 2 / (1 + e^{2x}) saturates correctly at both ends (e^{2x} -> inf / 0)
-__device__ __forceinline__ float sigmoidf_(float x) { return __frcp_rn(1.f + __expf(-x)); }
-__device__ __forceinline__ float tanhf_(float x) { return 1.f - 2.f * __frcp_rn(1.f + __expf(2.f * x)); }
 
 // two weight matrices -> bf16 planes, one launch: pair index p over (n0 + n1) / 2
 __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ w0, unsigned short* __restrict__ p0,
@@ -322,8 +318,8 @@ __global__ __launch_bounds__(w8::NT) void gru_cell_fwd_x3w8_kernel(
     const int lrow = wm + 8 * (i >> 2) + 4 * lh + (i & 3);
     const int row = m0 + lrow;
     const float pr = acc[0][i] + b_r, pz = acc[1][i] + b_z, gin = acc[2][i] + b_in, ghn = acc[3][i] + b_hn;
-    const float rr = sigmoidf_(pr), zz = sigmoidf_(pz);
-    const float nn = tanhf_(fmaf(rr, ghn, gin));
+    const float rr = fast_sigmoid(pr), zz = fast_sigmoid(pz);
+    const float nn = fast_tanh(fmaf(rr, ghn, gin));
     float* hp = sH + lrow * ST + wc + l32;
     *hp = fmaf(zz, *hp - nn, nn);                          // every element of the tile has exactly one owner lane
     if (SAVE && row < N) {

@@ -17,6 +17,7 @@
 // `s_waitcnt vmcnt(0)` of the barrier that ends it.
 #include "bf16x3.h"
 #include "common.h"
+#include "gru_gates.h"
 #include "uavgnn_probe.h"
 
 namespace uavgnn {
@@ -25,9 +26,6 @@ namespace {
 using namespace x3;
 constexpr int BM = 128, BK = 32, BJ = 64, NT = 512, ST = 68;
 constexpr int PA = BM * 4, PB = 3 * BJ * 4;            // 16-byte chunks per split plane of the A / B tile
-
-__device__ __forceinline__ float sigmoidf_(float x) { return __frcp_rn(1.f + __expf(-x)); }
-__device__ __forceinline__ float tanhf_(float x) { return 1.f - 2.f * __frcp_rn(1.f + __expf(2.f * x)); }
 
 // 64 consecutive 16-byte chunks: global (per lane) -> LDS (wave-uniform base + 16 lane)
 __device__ __forceinline__ void glds16(const u32x4* g, u32x4* l) {
@@ -281,8 +279,8 @@ __global__ __launch_bounds__(NT) void gru_cell_fwd_planes_kernel(const u32x4* __
     const int lrow = wm + 8 * (i >> 2) + 4 * lh + (i & 3);
     const int row = m0 + lrow;
     const float pr = acc[0][i] + b_r, pz = acc[1][i] + b_z, gin = acc[2][i] + b_in, ghn = acc[3][i] + b_hn;
-    const float rr = sigmoidf_(pr), zz = sigmoidf_(pz);
-    const float nn = tanhf_(fmaf(rr, ghn, gin));
+    const float rr = fast_sigmoid(pr), zz = fast_sigmoid(pz);
+    const float nn = fast_tanh(fmaf(rr, ghn, gin));
     float* hp = sH + lrow * ST + wc + l32;
     *hp = fmaf(zz, *hp - nn, nn);
     if (SAVE && row < N) {

@@ -19,7 +19,6 @@ K1_BF16Z = os.environ.get("UAVGNN_K1_BF16Z", "1") != "0"
 # row maxima out of the time-batched K1 launches (more than K1_ROWMAX_MIN_ROWS destinations) for an f16x2 f_aggr forward (A/B switch)
 K1_ROWMAX = os.environ.get("UAVGNN_K1_ROWMAX", "1") != "0"
 K1_ROWMAX_MIN_ROWS = 1 << 17
-GEMM_H2_RM2 = os.environ.get("UAVGNN_GEMM_H2_RM2", "1") != "0"   # d x of the recurrent step takes the row maxima of d_proj inside its launch (A/B switch: a pass of uavgnn_row_absmax)
 # ... and out of ANY launch whose `seen` relation has this mean in-degree (a compute-bound launch) from the row count at which the f_aggr
 # product behind it takes the f16x2 kernel (GEMM_X3_SMALL_GRID tiles of 256 x 128 for H = 256 output columns)
 K1_ROWMAX_DENSE_DEG = int(os.environ.get("UAVGNN_K1_ROWMAX_DENSE_DEG", "16"))
@@ -352,6 +351,11 @@ def gru_gates(gi, gh, h):
     return _GruGates.apply(gi, gh, h)
 
 
+def _mc_operand(t) -> bool:
+    """What every matrix-core wrapper asks of a row-major fp32 operand: unit inner stride, rows of whole float4s, a 16-byte base."""
+    return t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
+
+
 GRU_FUSED = True   # K4 as one kernel (csrc/gru_fused.hip); False: vendor GEMMs + the gate kernel (A/B, tools/gru_probe.py)
 
 
@@ -359,8 +363,7 @@ GRU_FUSED_MIN_ROWS = 1024   # below: a handful of workgroups walk 18 K slices se
 
 
 def gru_cell_supported(inp, h) -> bool:
-    return bool(GRU_FUSED and inp.shape[0] >= GRU_FUSED_MIN_ROWS and inp.is_cuda and inp.dtype == th.float32 and h.dtype == th.float32 and inp.stride(1) == 1
-                and inp.stride(0) % 4 == 0 and inp.data_ptr() % 16 == 0
+    return bool(GRU_FUSED and inp.shape[0] >= GRU_FUSED_MIN_ROWS and inp.is_cuda and inp.dtype == th.float32 and h.dtype == th.float32 and _mc_operand(inp)
                 and L.lib().uavgnn_gru_cell_supported(inp.shape[1], h.shape[1]))
 
 
@@ -434,8 +437,7 @@ def gru_cell_two_piece_supported(x, c, h) -> bool:
     """The bf16x3 cell takes its input as [x || c] from two buffers (no concatenated copy) when both pieces are multiples of
     32 columns wide, 16-byte aligned with row strides of whole float4s."""
     K1, K2, H = x.shape[1], c.shape[1], h.shape[1]
-    return bool(GRU_X3 and K1 >= 32 and K1 % 32 == 0 and K2 % 32 == 0 and x.stride(1) == 1 and c.stride(1) == 1
-                and x.stride(0) % 4 == 0 and c.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 and c.data_ptr() % 16 == 0
+    return bool(GRU_X3 and K1 >= 32 and K1 % 32 == 0 and K2 % 32 == 0 and _mc_operand(x) and _mc_operand(c)
                 and L.lib().uavgnn_gru_cell_x3_supported(K1 + K2, H)
                 and 4 * x.shape[0] * max(x.stride(0), c.stride(0), H) < 2 ** 32)
 
@@ -493,11 +495,6 @@ def _gru_cell_launch(inp, h, W_ih, b_ih, W_hh, b_hh, save, inp2=None, h2_out=Non
                                          L.stream())
     L.check(rc, "uavgnn_gru_cell_fwd")
     return h2, pre
-
-
-DINP_SPLIT = os.environ.get("UAVGNN_DINP_SPLIT", "1") != "0"   # _TarmacStep.backward: d x and d c of the GRU input as two products
-# A/B switch: UAVGNN_HEAD_FUSED_BWD=0 forms d h' = d_hout + dq W_out with a vendor GEMM in front of the gate kernel
-HEAD_FUSED_BWD = os.environ.get("UAVGNN_HEAD_FUSED_BWD", "1") != "0"
 
 
 def _gru_gates_bwd_from_pre(pre, h, d_hout, d_gi=None, d_gh=None, head=None, sums=None, rowmax=None):
@@ -637,8 +634,7 @@ GEMM_X3_SMALL_GRID = 128   # fewer 256 x 128 tiles than this: 128 x 128 tiles in
 
 
 def gemm_x3_supported(a, n_out, k) -> bool:
-    return bool(GEMM_X3 and a.is_cuda and a.dtype == th.float32 and a.dim() == 2 and a.stride(1) == 1
-                and a.stride(0) % 4 == 0 and a.data_ptr() % 16 == 0 and n_out % 128 == 0 and a.shape[0] >= 4096
+    return bool(GEMM_X3 and a.is_cuda and a.dtype == th.float32 and a.dim() == 2 and _mc_operand(a) and n_out % 128 == 0 and a.shape[0] >= 4096
                 and a.shape[0] * a.stride(0) < 2 ** 31 and L.lib().uavgnn_gemm_x3_supported(a.shape[0], n_out, k))
 
 
@@ -700,14 +696,10 @@ def _mm_nn(dy, W, out=None, accumulate=False, rowmax=None):
     return out.addmm_(dy, W) if accumulate else th.mm(dy, W, out=out)
 
 
-GATE_SUMS = os.environ.get("UAVGNN_GATE_SUMS", "1") != "0"   # bias gradients of the cell from the gate kernel's column sums (A/B switch)
-DX_CAT = os.environ.get("UAVGNN_DX_CAT", "1") != "0"   # d x of the TarMAC step as ONE product over [d_gi || d_proj] (A/B switch)
-
-
 def gemm_x3_cat_supported(a1, a2, n_out) -> bool:
     K1, K2 = a1.shape[1], a2.shape[1]
-    return bool(DX_CAT and a2.is_cuda and a2.dtype == th.float32 and a2.dim() == 2 and a2.shape[0] == a1.shape[0] and K1 % 32 == 0
-                and K2 % 32 == 0 and a2.stride(1) == 1 and a2.stride(0) % 4 == 0 and a2.data_ptr() % 16 == 0
+    return bool(a2.is_cuda and a2.dtype == th.float32 and a2.dim() == 2 and a2.shape[0] == a1.shape[0] and K1 % 32 == 0
+                and K2 % 32 == 0 and _mc_operand(a2)
                 and a2.shape[0] * a2.stride(0) < 2 ** 31 and gemm_x3_supported(a1, n_out, K1 + K2)
                 and ((a1.shape[0] + 255) // 256) * ((n_out + 127) // 128) >= GEMM_X3_SMALL_GRID and not (GEMM_X3_FLAGS & 8))
 
@@ -796,8 +788,8 @@ GEMM_H2_N64_MIN_GRID = 128   # fewer 128 x 64 tiles than this (half the CUs): th
 
 def gemm_h2_n64_supported(a, n_out, k) -> bool:
     """The 128 x 64-tile f16x2 kernel covers y = a B^T with n_out % 64 == 0 on a grid that fills at least half the chip."""
-    return bool(DC_H2 and GEMM_H2 and a.is_cuda and a.dtype == th.float32 and a.dim() == 2 and a.stride(1) == 1 and a.shape[1] == k
-                and a.stride(0) % 4 == 0 and a.data_ptr() % 16 == 0 and n_out % 64 == 0 and k % 64 == 0 and a.shape[0] * a.stride(0) < 2 ** 31
+    return bool(DC_H2 and GEMM_H2 and a.is_cuda and a.dtype == th.float32 and a.dim() == 2 and _mc_operand(a) and a.shape[1] == k
+                and n_out % 64 == 0 and k % 64 == 0 and a.shape[0] * a.stride(0) < 2 ** 31
                 and L.lib().uavgnn_gemm_h2_supported(a.shape[0], n_out, k)
                 and ((a.shape[0] + 127) // 128) * (n_out // 64) >= GEMM_H2_N64_MIN_GRID)
 
@@ -821,13 +813,14 @@ def gemm_h2_n64(a, W, rowmax, out=None):
     return out
 
 
-GEMM_TN_X3 = os.environ.get("UAVGNN_GEMM_TN_X3", "1") != "0"   # weight gradients on the bf16 matrix cores (csrc/gemm_tn_x3.hip)
+# Weight gradients on the bf16 matrix cores (csrc/gemm_tn_x3.hip).
 # Measured against the vendor's batched split-K fp32 GEMM (tools/gemm_tn_probe.py, profiles/r03_gemm_tn_probe.txt): BOTH operands
 # have to be split and transposed inside the kernel, which bounds it at 95-108 TFLOP/s fp32-equivalent = the vendor's 106-108
 # at the per-step shapes (32 768 rows; 0.4-0.6 x on the 96- and 9-row outputs), 142 vs 134 at the time-batched encoder shape
 # (1.67 M rows).  Only the latter takes the kernel; its error against float64 is 0.5-0.8 x the vendor's on every shape.
 GEMM_TN_MIN_ROWS = 1 << 18
 # ... on the f16x2 arithmetic with LDS transposing reads (csrc/gemm_tn_h2.hip): the recurrent weights of a staged BPTT sequence
+# (A/B switch: bench.py's result line names UAVGNN_GEMM_TN_H2=0 as the way back to bf16x3 / the vendor GEMM)
 GEMM_TN_H2 = os.environ.get("UAVGNN_GEMM_TN_H2", "1") != "0"
 
 
@@ -845,14 +838,13 @@ def gemm_tn_h2_supported(dy, x, min_in=128) -> bool:
     """dy^T x on csrc/gemm_tn_h2.hip (256 x 128 output tiles).  min_in: the narrowest `x` worth a 128-wide tile - 128 by default; the
     96-column projections pass 96 with the operands SWAPPED (x^T d_proj = dWp^T: three quarters of a tile instead of three eighths)."""
     return bool(GEMM_X3 and GEMM_H2 and GEMM_TN_H2 and dy.is_cuda and dy.dtype == th.float32 and x.dtype == th.float32 and dy.dim() == 2
-                and x.dim() == 2 and dy.shape[0] == x.shape[0] and dy.shape[0] >= GEMM_TN_MIN_ROWS and dy.stride(1) == 1 and x.stride(1) == 1
-                and dy.stride(0) % 4 == 0 and x.stride(0) % 4 == 0 and dy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0
+                and x.dim() == 2 and dy.shape[0] == x.shape[0] and dy.shape[0] >= GEMM_TN_MIN_ROWS and _mc_operand(dy) and _mc_operand(x)
                 and dy.shape[1] >= 256 and x.shape[1] >= min_in       # (a 9-row output leaves most of a 256 x 128 tile idle: the vendor GEMM)
                 and L.lib().uavgnn_gemm_tn_h2_supported(dy.shape[0], dy.shape[1], x.shape[1]))
 
 
 def gemm_tn_x3_supported(dy, x) -> bool:
-    return bool(GEMM_X3 and GEMM_TN_X3 and dy.is_cuda and dy.dtype == th.float32 and x.dtype == th.float32 and dy.dim() == 2
+    return bool(GEMM_X3 and dy.is_cuda and dy.dtype == th.float32 and x.dtype == th.float32 and dy.dim() == 2
                 and x.dim() == 2 and dy.shape[0] == x.shape[0] and dy.shape[0] >= GEMM_TN_MIN_ROWS and dy.stride(1) == 1
                 and x.stride(1) == 1 and dy.shape[1] > 0 and x.shape[1] > 0)
 
@@ -911,10 +903,7 @@ class _LinearSplitK(th.autograd.Function):
         elif ctx.needs_input_grad[1] and gemm_tn_x3_supported(dy, x):
             dW = gemm_tn_x3(dy, x).sum(0)
         elif ctx.needs_input_grad[1]:
-            n = x.shape[0]
-            S = 1   # row chunks of >= 2048: S = 16 at N_a = 32768 (measured best or within 10 % on every layer shape)
-            while S < 64 and n % (2 * S) == 0 and n // (2 * S) >= 2048:
-                S *= 2
+            n, S = x.shape[0], WeightGradSink._chunks(x.shape[0])
             if S > 1:
                 xc = x if x.is_contiguous() else x.contiguous()
                 part = th.bmm(dy.view(S, n // S, -1).transpose(1, 2), xc.view(S, n // S, -1))   # [S, out, in]
@@ -968,9 +957,8 @@ class _LinearReLU(th.autograd.Function):
         x, W, y = ctx.saved_tensors
         n, C = dy.shape
         if (RELU_BWD_FUSED and ctx.needs_input_grad[2] and dy.is_cuda and dy.dtype == th.float32 and y.dtype == th.float32 and n > 0
-                and C % 4 == 0 and dy.stride(1) == 1 and y.stride(1) == 1 and dy.stride(0) % 4 == 0 and y.stride(0) % 4 == 0
-                and dy.stride(0) >= C and y.stride(0) >= C      # a row-broadcast gradient (stride 0) takes the torch path below
-                and dy.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0):
+                and C % 4 == 0 and _mc_operand(dy) and _mc_operand(y)
+                and dy.stride(0) >= C and y.stride(0) >= C):      # a row-broadcast gradient (stride 0) takes the torch path below
             # the mask and the bias gradient in ONE pass over the gradient (csrc/colsum.hip): autograd's threshold_backward + sum
             # are two (5.1 + 1.7 GB per C3 update on the time-batched encoder)
             S = _row_blocks(n)
@@ -1108,6 +1096,7 @@ class WeightGradSink:
 
     @staticmethod
     def _chunks(n):
+        """row chunks of >= 2048: S = 16 at N_a = 32768 (measured best or within 10 % on every layer shape)"""
         S = 1
         while S < 64 and n % (2 * S) == 0 and n // (2 * S) >= 2048:
             S *= 2
@@ -1176,73 +1165,86 @@ class WeightGradSink:
     # (autograd of gnn_agents.py:243-246,:56 under learner.py:157).
     def begin_sequence(self, T1, N, x_all):
         """x_all: the time-major [T1 * N, H] input of the T1 recurrent steps (the time-batched encoder's output)."""
-        self.seq = _SequenceStage(T1, N, x_all.detach(), getattr(self, "_seq_bufs", None))
+        self.seq = _SequenceStage(T1, N, x_all.detach(), self._seq_bufs)
         self._seq_bufs = self.seq.bufs          # the buffers are reused by the next sequence (chunks of one accumulate)
 
     def end_sequence(self):
-        seq, self.seq = getattr(self, "seq", None), None
+        seq, self.seq = self.seq, None
         if seq is None or not seq.bwd_steps:
             return
-        T1, N = seq.T1, seq.N
+        T1, N, H = seq.T1, seq.N, seq.H
         full = sorted(seq.bwd_steps) == list(range(T1)) and seq.t_fwd == T1
-        if full and 0 < len(seq.g4_steps) < T1:
+        if full and len({seq.steps[t].packed for t in range(T1)}) > 1:
             full = False         # packed and plain gate-gradient slots in one sequence (never from one caller): reduce per step
         spans = [(0, T1)] if full else [(t, t + 1) for t in sorted(seq.bwd_steps)]
-        split, ids, H = seq.split, seq.ids, seq.H
         for (t0, t1) in spans:
             rows = lambda name, lo=0: seq.bufs[name][t0 + lo:t1 + lo].reshape((t1 - t0) * N, -1)   # noqa: E731
-            d_proj = rows("d_proj")
-            g4 = t0 in seq.g4_steps
-            if g4:
-                # G = [dn_h | dr | dz | dn_i]: d_gi is a view; d_gh comes with its column blocks in the order n, r, z, so dW_hh is
-                # accumulated with its row blocks in that order (a slot of its own) and put back in order once, at flush
+            recs = [seq.steps[t] for t in range(t0, t1)]
+            packed = recs[0].packed
+            if packed:      # G = [dn_h | dr | dz | dn_i]: d_gi is a view; d_gh comes with its column blocks in the order n, r, z
                 d_gi, d_gh = rows("g4")[:, H:], rows("g4")[:, :3 * H]
-                whh_key, whh_flush = "W_hh_nrz", lambda g: split("W_hh", th.cat((g[H:], g[:H]), 0), 0)
             else:
                 d_gi, d_gh = rows("d_gi"), rows("d_gh")
-                whh_key, whh_flush = "W_hh", lambda g: split("W_hh", g, 0)
-            dq = seq.dq_rows(t0, t1)
-            x = seq.x_all[t0 * N:t1 * N]
-            h, h2, inp = rows("h"), rows("h", 1), rows("inp")
-            # the vendor's batched split-K fp32 GEMM (64 row chunks): at these shapes - 768-, 96- and 9-row outputs over
+            bounds = gsum = None
+            if full and all(r.rowmax and r.rm_g for r in recs):
+                # the row maxima the message kernel (max over [x || c || h] per agent), the gate kernel (d_gi / d_gh) and the d x product
+                # (d_proj) left for the f16x2 cell / input-gradient products of every step
+                bounds = (seq.bufs["rowmax"][:T1], seq.bufs["rm_g"][:T1], seq.bufs["rm_p"][:T1] if all(r.rm_p for r in recs) else None)
+            if all(r.gsum for r in recs):
+                # the gate kernels of these steps left per-workgroup column sums d_r | d_z | d_n (input) | d_n (hidden): [., 4H]
+                gsum = seq.bufs["gsum"][t0:t1]
+                gsum = gsum.reshape(gsum.shape[0] * gsum.shape[1], 4 * H)
+            # allow_tn=False: the vendor's batched split-K fp32 GEMM (64 row chunks): at these shapes - 768-, 96- and 9-row outputs over
             # 1.67 M rows - it runs at 135-141 TFLOP/s against 85-107 for csrc/gemm_tn_x3.hip (tools/gemm_tn_big_probe.py),
             # and 25-30 % above its own per-step rate (32 768 rows per call)
-            tn = False
-            h2_bounds = full and seq.rowmax_steps >= set(range(T1)) and seq.rm_g_steps >= set(range(T1))
-            if h2_bounds and seq.rm_p_steps >= set(range(T1)) and gemm_tn_h2_supported(x, d_proj, 96) and gemm_tn_h2_supported(h, d_proj, 96):
-                # dWp on the f16x2 kernel with the operands swapped - x^T d_proj = (dWp_x)^T, [H x 96]: one 256 x 128 tile three quarters full
-                # (d_proj^T x would fill three eighths of two: slower than the vendor) - 0.93 -> 0.5 ms each against the vendor's 0.74;
-                # column bounds: the message kernel's row maxima bound x and h, the per-step row maxima of d_proj (taken for the d x
-                # product of the step) bound d_proj
-                bxh, bpj = _max_two_stage(seq.bufs["rowmax"][:T1]), _max_two_stage(seq.bufs["rm_p"][:T1])
-                self.weight_h2(("Wp_x", ids["Wp"]), x, d_proj, bxh, bpj, lambda g: split("Wp", g.t(), 0))
-                self.weight_h2(("Wp_h", ids["Wp"]), h, d_proj, bxh, bpj, lambda g: split("Wp", g.t(), H))
-            else:
-                self.weight(("Wp_x", ids["Wp"]), d_proj, x, lambda g: split("Wp", g, 0), tn)
-                self.weight(("Wp_h", ids["Wp"]), d_proj, h, lambda g: split("Wp", g, H), tn)
-            self.bias(("bp", ids["Wp"]), d_proj, lambda g: split("bp", g, 0))
-            if h2_bounds and gemm_tn_h2_supported(d_gi, inp) and gemm_tn_h2_supported(d_gh, h):
-                # dW_ih / dW_hh on the f16x2 kernel (177-187 TFLOP/s against the vendor's 131-143 at C3): the column scales of the split
-                # come for free - the row maxima the message kernel (max over [x || c || h] per agent) and the gate kernel (d_gi / d_gh) left
-                # for the f16x2 cell / input-gradient products bound every column; a column far below the global maximum is held with fewer
-                # bits (absolute error <= 2^-39 of the bound per element, averaged down over 10^6 rows: DESIGN.md section 5)
-                bx, by = _max_two_stage(seq.bufs["rowmax"][:T1]), _max_two_stage(seq.bufs["rm_g"][:T1])
-                self.weight_h2(("W_ih", ids["W_ih"]), d_gi, inp, by, bx, lambda g: split("W_ih", g, 0))
-                self.weight_h2((whh_key, ids["W_hh"]), d_gh, h, by, bx, whh_flush)
-            else:
-                self.weight(("W_ih", ids["W_ih"]), d_gi, inp, lambda g: split("W_ih", g, 0), tn)
-                self.weight((whh_key, ids["W_hh"]), d_gh, h, whh_flush, tn)
-            if all(t in seq.gsum_steps for t in range(t0, t1)):
-                # the gate kernels of these steps left per-workgroup column sums d_r | d_z | d_n (input) | d_n (hidden): [., 4H]
-                gs = seq.bufs["gsum"][t0:t1]
-                gs = gs.reshape(gs.shape[0] * gs.shape[1], 4 * H)
-                self.bias(("b_ih", ids["W_ih"]), gs[:, :3 * H], lambda g: split("b_ih", g, 0))
-                self.bias(("b_hh_n", ids["W_hh"]), gs[:, 3 * H:], lambda g: split("b_hh", g, 2 * H))
-            else:
-                self.bias(("b_ih", ids["W_ih"]), d_gi, lambda g: split("b_ih", g, 0))
-                self.bias(("b_hh_n", ids["W_hh"]), d_gh[:, :H] if g4 else d_gh[:, 2 * H:], lambda g: split("b_hh", g, 2 * H))
-            self.weight(("W_out", ids["W_out"]), dq, h2, lambda g: split("W_out", g, 0), tn)
-            self.bias(("b_out", ids["W_out"]), dq, lambda g: split("b_out", g, 0))
+            self.step_grads(seq.split, seq.ids, H, seq.x_all[t0 * N:t1 * N], rows("h"), rows("h", 1), rows("inp"), rows("d_proj"), d_gi, d_gh,
+                            seq.dq_rows(t0, t1), packed=packed, gsum=gsum, bounds=bounds, allow_tn=False)
+
+    def step_grads(self, split, ids, H, x, h, h2, inp, d_proj, d_gi, d_gh, dq, packed=False, gsum=None, bounds=None, allow_tn=True):
+        """The nine parameter gradients of the recurrent step - Wp (its x and h halves), bp, W_ih, b_ih, W_hh, b_hh (n block), W_out,
+        b_out - over the rows handed in: the tensors of ONE step, or slot views over a span of steps of a staged sequence.
+        split: the step's flush target; ids: {"Wp", "W_ih", "W_hh", "W_out"} -> identity of the parameter (the slot keys).
+        packed: d_gi / d_gh are views of G = [dn_h | dr | dz | dn_i] - d_gh has its column blocks in the order n, r, z.
+        gsum [., 4H]: the gate kernels' column-sum partials d_r | d_z | d_n (input) | d_n (hidden), instead of passes over d_gi / d_gh.
+        bounds = (row maxima of [x || c || h], of d_gi / d_gh, of d_proj or None) of every row handed in: the weight gradients on the
+        f16x2 kernel (csrc/gemm_tn_h2.hip) where it covers the shape."""
+        if packed:
+            # dW_hh is accumulated with its row blocks in the order n, r, z (a slot of its own) and put back in order once, at flush
+            whh_key, whh_flush = "W_hh_nrz", lambda g: split("W_hh", th.cat((g[H:], g[:H]), 0), 0)
+        else:
+            whh_key, whh_flush = "W_hh", lambda g: split("W_hh", g, 0)
+        rm_x, rm_g, rm_p = bounds if bounds is not None else (None, None, None)
+        if rm_p is not None and gemm_tn_h2_supported(x, d_proj, 96) and gemm_tn_h2_supported(h, d_proj, 96):
+            # dWp on the f16x2 kernel with the operands swapped - x^T d_proj = (dWp_x)^T, [H x 96]: one 256 x 128 tile three quarters full
+            # (d_proj^T x would fill three eighths of two: slower than the vendor) - 0.93 -> 0.5 ms each against the vendor's 0.74;
+            # column bounds: the message kernel's row maxima bound x and h, the per-step row maxima of d_proj (taken for the d x
+            # product of the step) bound d_proj
+            bxh, bpj = _max_two_stage(rm_x), _max_two_stage(rm_p)
+            self.weight_h2(("Wp_x", ids["Wp"]), x, d_proj, bxh, bpj, lambda g: split("Wp", g.t(), 0))
+            self.weight_h2(("Wp_h", ids["Wp"]), h, d_proj, bxh, bpj, lambda g: split("Wp", g.t(), H))
+        else:
+            self.weight(("Wp_x", ids["Wp"]), d_proj, x, lambda g: split("Wp", g, 0), allow_tn)
+            self.weight(("Wp_h", ids["Wp"]), d_proj, h, lambda g: split("Wp", g, H), allow_tn)
+        self.bias(("bp", ids["Wp"]), d_proj, lambda g: split("bp", g, 0))
+        if bounds is not None and gemm_tn_h2_supported(d_gi, inp) and gemm_tn_h2_supported(d_gh, h):
+            # dW_ih / dW_hh on the f16x2 kernel (177-187 TFLOP/s against the vendor's 131-143 at C3): the column scales of the split
+            # come for free - the global maxima of the row maxima bound every column; a column far below the global maximum is held with
+            # fewer bits (absolute error <= 2^-39 of the bound per element, averaged down over 10^6 rows: DESIGN.md section 5)
+            bx, by = _max_two_stage(rm_x), _max_two_stage(rm_g)
+            self.weight_h2(("W_ih", ids["W_ih"]), d_gi, inp, by, bx, lambda g: split("W_ih", g, 0))
+            self.weight_h2((whh_key, ids["W_hh"]), d_gh, h, by, bx, whh_flush)
+        else:
+            self.weight(("W_ih", ids["W_ih"]), d_gi, inp, lambda g: split("W_ih", g, 0), allow_tn)
+            self.weight((whh_key, ids["W_hh"]), d_gh, h, whh_flush, allow_tn)
+        if gsum is not None:
+            self.bias(("b_ih", ids["W_ih"]), gsum[:, :3 * H], lambda g: split("b_ih", g, 0))
+            self.bias(("b_hh_n", ids["W_hh"]), gsum[:, 3 * H:], lambda g: split("b_hh", g, 2 * H))
+        else:
+            # d_gh == d_gi on the r and z columns: only the n block of b_hh needs its own pass over d_gh
+            self.bias(("b_ih", ids["W_ih"]), d_gi, lambda g: split("b_ih", g, 0))
+            self.bias(("b_hh_n", ids["W_hh"]), d_gh[:, :H] if packed else d_gh[:, 2 * H:], lambda g: split("b_hh", g, 2 * H))
+        self.weight(("W_out", ids["W_out"]), dq, h2, lambda g: split("W_out", g, 0), allow_tn)
+        self.bias(("b_out", ids["W_out"]), dq, lambda g: split("b_out", g, 0))
 
     def flush(self):
         self.end_sequence()
@@ -1254,6 +1256,18 @@ class WeightGradSink:
         self._seq_bufs = None
 
 
+class _StepRecord:
+    """What ONE step of a staged sequence left in its slots: `rowmax` by the forward's message kernel (row maxima of [x || c || h]);
+    by the backward's gate kernel `gsum` (its column-sum partials), `rm_g` (row maxima of d_gi / d_gh) and `packed` (ONE [N, 4H] "g4"
+    slot instead of "d_gi" / "d_gh"); `rm_p` (row maxima of d_proj) by the d x product; `dq`: the gradient of the step's Q values as
+    autograd handed it over."""
+    __slots__ = ("rowmax", "gsum", "rm_g", "packed", "rm_p", "dq")
+
+    def __init__(self):
+        self.rowmax = self.gsum = self.rm_g = self.packed = self.rm_p = False
+        self.dq = None
+
+
 class _SequenceStage:
     """Slots of the time-batched buffers of one BPTT sequence (WeightGradSink.begin_sequence)."""
 
@@ -1261,13 +1275,8 @@ class _SequenceStage:
         self.T1, self.N, self.x_all = T1, N, x_all
         self.bufs = bufs if bufs is not None else {}
         self.t_fwd = 0
-        self.bwd_steps = []
-        self.gsum_steps = set()          # steps whose gate kernel wrote its column-sum partials ("gsum" slots)
-        self.rowmax_steps = set()        # steps whose message kernel left the row maxima of [x || c || h] ("rowmax" slots)
-        self.rm_g_steps = set()          # steps whose gate kernel left the row maxima of d_gi / d_gh ("rm_g" slots)
-        self.g4_steps = set()            # steps whose gate kernel wrote ONE packed [N, 4H] buffer ("g4" slots) instead of "d_gi" / "d_gh"
-        self.rm_p_steps = set()          # steps whose backward took the row maxima of d_proj ("rm_p" slots)
-        self.dq_steps = {}               # step -> the gradient of the step's Q values as autograd handed it over
+        self.steps = {}                  # step -> _StepRecord: what its forward and backward left in the slots
+        self.bwd_steps = []              # steps whose backward ran staged, in that order
         self.split = self.ids = self.H = None
 
     def dq_rows(self, t0, t1):
@@ -1275,7 +1284,7 @@ class _SequenceStage:
         normally consecutive [N, A] slices of ONE buffer (the backward of the learner's stack of the per-step Q values): then the rows are
         a view of it - rounds 4-5 copied every step into a staging slot (51 launches of 4.7 us per update); anything else is gathered by
         one torch.cat."""
-        parts = [self.dq_steps[t] for t in range(t0, t1)]
+        parts = [self.steps[t].dq for t in range(t0, t1)]
         if len(parts) == 1:
             return parts[0] if parts[0].is_contiguous() else parts[0].contiguous()
         first, (N, A) = parts[0], parts[0].shape
@@ -1397,15 +1406,11 @@ def _launch_tarmac_msg(msg, x, h, bp, M, K, talk_off, talk_src, N, H, c_ptr, ld_
     L.check(rc, "uavgnn_tarmac_msg_fwd")
 
 
-HEAD_KERNEL = os.environ.get("UAVGNN_HEAD_KERNEL", "1") != "0"   # the Q head on csrc/head.hip (one pass over h'); 0: vendor GEMM
-
-
 def head_fwd(h, W_out, b_out):
     """q = h W_out^T + b_out (gnn_agents.py:56), no autograd: csrc/head.hip for n_actions <= 16, else the vendor GEMM."""
     N, H = h.shape
     A = W_out.shape[0]
-    if (HEAD_KERNEL and h.is_cuda and h.dtype == th.float32 and N > 0 and h.stride(1) == 1 and W_out.stride(1) == 1
-            and h.stride(0) % 4 == 0 and W_out.stride(0) % 4 == 0 and h.data_ptr() % 16 == 0 and W_out.data_ptr() % 16 == 0
+    if (h.is_cuda and h.dtype == th.float32 and N > 0 and _mc_operand(h) and _mc_operand(W_out)
             and b_out.is_contiguous() and L.lib().uavgnn_head_supported(H, A)):
         q = th.empty((N, A), dtype=th.float32, device=h.device)
         with KERNEL_TIMER.span("head_fwd", (N, H, A)):
@@ -1481,6 +1486,7 @@ class _TarmacStep(th.autograd.Function):
             if seq is not None:
                 seq_t = seq.t_fwd
                 seq.t_fwd += 1
+                seq.steps[seq_t] = _StepRecord()
                 inp = seq.slot("inp", seq_t, H + M)
                 if seq_t == 0:
                     seq.slot("h", 0, H, extra=1).copy_(h)
@@ -1488,7 +1494,7 @@ class _TarmacStep(th.autograd.Function):
                 inp = th.empty((N, H + M), dtype=th.float32, device=x.device)     # [x || c], both halves filled by K3b
             if seq is not None and rowmax is not None:       # kept for the sequence: its maximum scales the weight-gradient products
                 rowmax = seq.slot("rowmax", seq_t, 1).view(N)
-                seq.rowmax_steps.add(seq_t)
+                seq.steps[seq_t].rowmax = True
             if msg is not None:     # proj, the attention weights and the x half of [x || c] are the launch's training outputs
                 proj = th.empty((N, ld), dtype=th.float32, device=x.device)
                 _launch_tarmac_msg(msg, x, h, bp, M, K, talk_off, talk_src, N, H, inp.data_ptr() + 4 * H, H + M, a_save.data_ptr(),
@@ -1527,146 +1533,24 @@ class _TarmacStep(th.autograd.Function):
     def backward(ctx, dq, dh2):
         (x, h, proj, inp, gi, gh, h2, a_save, Wp, W_ih, W_hh, W_out, talk_off, talk_src, t_off, t_dst,
          t_pos) = ctx.saved_tensors
-        M, K = ctx.dims
         N, H = x.shape
         if not ctx.have_pre:    # gi would be the [N, H] placeholder: reading 4H floats per row from it is out of bounds
             raise L.UavGnnError("tarmac_step: backward through a forward that saved no pre-activations (train=False)")
         sink = GRAD_SINK
-        rm_g = g4 = None
         dq = L.f32c(dq) if dq is not None else th.zeros((N, W_out.shape[0]), dtype=th.float32, device=x.device)
-        # d h' = d_hout + dq W_out inside the gate kernel when the cell ran fused (its pre-activation sets are what that kernel reads)
-        head = None
-        if (HEAD_FUSED_BWD and ctx.fused_gru and H % 4 == 0 and W_out.shape[0] <= 64 and W_out.is_contiguous()
-                and W_out.dtype == th.float32 and W_out.data_ptr() % 16 == 0
-                and (dh2 is None or (dh2.is_contiguous() and dh2.dtype == th.float32 and dh2.shape == (N, H)))):
-            head = (dq, W_out.detach())
-            dh2_tot = dh2
-            if sink is not None:
-                sink.owned.clear()
-        elif dh2 is None:
-            dh2_tot = th.mm(dq, W_out)
-        elif (sink is not None and dh2.is_contiguous() and dh2.dtype == th.float32 and dh2.shape == (N, H)
-              and sink.owned.get(dh2.data_ptr()) is not None):
-            # inside the learner's BPTT the incoming d h' is the buffer the NEXT step's backward of this very op
-            # allocated and returned (registered in sink.owned and kept alive there): nobody else holds it, so accumulate
-            # in place instead of copying 33 MB into a fresh output first.  Any other gradient tensor (a hook's,
-            # retain_grad's, one autograd summed from several consumers) lives at another address and is left untouched.
-            sink.owned.clear()
-            dh2_tot = dh2.addmm_(dq, W_out)
-        else:
-            dh2_tot = th.addmm(dh2, dq, W_out)
         seq = ctx.seq if (sink is not None and ctx.seq is not None and sink.seq is ctx.seq) else None
-        if seq is not None:      # staged sequence: the gate gradients go straight into the time-batched buffers
-            t = ctx.seq_t
-            G = L.lib().uavgnn_gru_gates_bwd_sum_rows(N, H) if GATE_SUMS else 0
-            sums = None
-            if G and (head is not None or dh2_tot is not None):
-                # the step's share of db_ih / db_hh comes out of the gate kernel: end_sequence() sums [T1 G, 4H] partials instead of
-                # streaming the [T1 N, 3H] gate gradients twice more
-                sums = seq.slot("gsum", t, 4 * H, rows=G)
-                seq.gsum_steps.add(t)
-            rm_g = None
-            if sums is not None and H == 256 and W_hh.stride(1) == 1:
-                if G4 and gemm_h2_supported(seq.slot("g4", t, 4 * H)[:, H:], H, 3 * H):
-                    g4 = seq.slot("g4", t, 4 * H)          # ONE buffer [dn_h | dr | dz | dn_i]: the r / z columns are stored once
-                    seq.g4_steps.add(t)
-                if g4 is not None or gemm_h2_supported(seq.slot("d_gh", t, 3 * H), H, 3 * H):
-                    rm_g = seq.slot("rm_g", t, 1).view(N)  # row maxima of d_gi / d_gh for the f16x2 products below (and, over the whole
-                    seq.rm_g_steps.add(t)                  # sequence, for the weight gradients)
-            if g4 is not None:
-                # packed mode of the gate entry: d_gi == d_gh + H.  d_gi = G[:, H:] in its natural order; `d_gh` is NOT the plain
-                # operand (its column blocks come in the order n, r, z): d h below takes it as two sources
-                d_gi, _, dh = _gru_gates_bwd_from_pre(gi, h, dh2_tot, g4[:, H:], g4[:, :3 * H], head=head, sums=sums, rowmax=rm_g)
-                d_gh = None
-            else:
-                d_gi, d_gh, dh = _gru_gates_bwd_from_pre(gi, h, dh2_tot, seq.slot("d_gi", t, 3 * H), seq.slot("d_gh", t, 3 * H),
-                                                         head=head, sums=sums, rowmax=rm_g)
-        elif ctx.fused_gru:
-            d_gi, d_gh, dh = _gru_gates_bwd_from_pre(gi, h, dh2_tot, head=head)      # gi holds the saved pre-activation sets
-        else:
-            d_gi, d_gh, dh = th.empty_like(gi), th.empty_like(gh), th.empty_like(h)
-            with KERNEL_TIMER.span("gru_gates_bwd"):
-                rc = L.lib().uavgnn_gru_gates_bwd(gi.data_ptr(), gh.data_ptr(), h.data_ptr(), dh2_tot.data_ptr(), N, H,
-                                                  d_gi.data_ptr(), d_gh.data_ptr(), dh.data_ptr(), L.stream())
-            L.check(rc, "uavgnn_gru_gates_bwd")
-        # d_inp = d_gi W_ih is [N, H + M]: d x | d c.  When the bf16x3 GEMM has the H-column shape, the two halves are separate
-        # products: d x lands where the caller wants it (the slice of the time-split gradient buffer) and the projection term is
-        # accumulated into it in place - no [N, H] copy in front of the addmm, and 256 of the 320 columns leave the vendor's
-        # 64 x 32-tile solution (134 us) for the matrix-core kernel (A/B: UAVGNN_DINP_SPLIT=0)
-        split_dinp = (DINP_SPLIT and M > 0 and W_ih.stride(1) == 1 and gemm_x3_supported(d_gi, H, W_ih.shape[0])
-                      and (ctx.dx_out is None or (ctx.dx_out.stride(1) == 1 and ctx.dx_out.dtype == th.float32)))
-        ld = M + 2 * K
-        d_proj = th.empty((N, ld), dtype=th.float32, device=x.device) if seq is None else seq.slot("d_proj", ctx.seq_t, ld)
-        dx_cat = False
-        if split_dinp:
-            dx = ctx.dx_out if ctx.dx_out is not None else th.empty((N, H), dtype=th.float32, device=x.device)
-            # d x = d_gi W_ih[:, :H] + d_proj Wp[:, :H]: ONE product over [d_gi || d_proj] once d_proj exists (behind the attention
-            # backward) instead of a product + an accumulating vendor GEMM that re-reads and re-writes d x (31 us per step)
-            dx_cat = Wp.stride(1) == 1 and gemm_x3_cat_supported(d_gi, d_proj, H)
-            if not dx_cat:
-                _mm_nn(d_gi, W_ih[:, :H], out=dx)
-            if rm_g is not None and M == 64 and gemm_h2_n64_supported(d_gi, M, 3 * H):
-                d_c = gemm_h2_n64(d_gi, W_ih[:, H:], rm_g)                 # [N, M], f16x2 on 128 x 64 tiles
-            else:
-                d_c = th.mm(d_gi, W_ih[:, H:])                             # [N, M]
-            d_c_ptr, d_c_ld = d_c.data_ptr(), M
-        else:
-            d_inp = _mm_nn(d_gi, W_ih)
-            d_c_ptr, d_c_ld = d_inp.data_ptr() + 4 * H, H + M
-        if g4 is not None:
-            # d h += d_gh W_hh over K in the order r, z, n as ever: [G[:, H:3H] || G[:, :H]] [W_hh[:2H]; W_hh[2H:]] (the stacked weight IS
-            # W_hh: the same planes and scales)
-            gemm_h2(g4[:, H:3 * H], W_hh[:2 * H], rm_g, True, out=dh, accumulate=True, a2=g4[:, :H], W2=W_hh[2 * H:])
-        else:
-            _mm_nn(d_gh, W_hh, out=dh, accumulate=True, rowmax=rm_g)
-        if sink is not None:
-            sink.owned.clear()
-            sink.owned[dh.data_ptr()] = dh
-        _launch_talk_bwd(ctx.env, proj.data_ptr() + 4 * M, ld, proj.data_ptr() + 4 * (M + K), ld, proj.data_ptr(), ld,
-                         K, M, talk_off, talk_src, (t_off, t_dst, t_pos), N, 1.0 / K, a_save, d_c_ptr,
-                         d_c_ld, d_proj.data_ptr() + 4 * M, ld, d_proj.data_ptr() + 4 * (M + K), ld, d_proj.data_ptr(),
-                         ld)
-        if dx_cat and rm_g is not None and gemm_h2_supported(d_gi, H, d_gi.shape[1] + d_proj.shape[1]):
-            # f16x2: the row scale of [d_gi || d_proj] is the larger of the gate kernel's bound and d_proj's own, which the launch takes
-            # itself (96 columns per row, read once more by its workgroups: a microsecond against a 7.8-us pass of uavgnn_row_absmax)
-            if seq is not None:      # kept for the sequence: the column bound of d_proj in the weight gradient dWp (end_sequence)
-                rm_p = seq.slot("rm_p", ctx.seq_t, 1).view(N)
-                seq.rm_p_steps.add(ctx.seq_t)
-            else:
-                rm_p = th.empty(N, dtype=th.float32, device=d_gi.device)
-            if GEMM_H2_RM2:
-                gemm_h2(d_gi, W_ih[:, :H], rm_g, True, out=dx, a2=d_proj, W2=Wp[:, :H], rowmax2_out=rm_p)
-            else:
-                gemm_h2(d_gi, W_ih[:, :H], rm_g, True, out=dx, a2=d_proj, W2=Wp[:, :H], rowmax2=row_absmax(d_proj, out=rm_p))
-        elif dx_cat:
-            gemm_x3_cat(d_gi, d_proj, W_ih[:, :H], Wp[:, :H], dx)
-        elif split_dinp:
-            dx.addmm_(d_proj, Wp[:, :H])                                   # h enters the projections stop-gradded
-        else:
-            dx = ctx.dx_out                                                # slice of the time-split gradient buffer
-            if dx is not None:
-                th.addmm(d_inp[:, :H], d_proj, Wp[:, :H], out=dx)
-            else:
-                dx = th.addmm(d_inp[:, :H], d_proj, Wp[:, :H])
+        head, dh2_tot = _step_dh2(ctx.fused_gru, sink, dq, dh2, W_out, N, H)
+        d_gi, d_gh, dh, rm_g, g4 = _step_gate_grads(seq, ctx.seq_t, ctx.fused_gru, gi, gh, h, dh2_tot, head, W_hh)
+        dx, d_proj = _step_input_grads(seq, ctx.seq_t, sink, ctx.dims, ctx.env, ctx.dx_out, proj, a_save, Wp, W_ih, W_hh,
+                                       (talk_off, talk_src, (t_off, t_dst, t_pos)), d_gi, d_gh, dh, rm_g, g4)
+        gWp = gbp = gWih = gbih = gWhh = gbhh = gWo = gbo = None
+        ids = {"Wp": id(Wp), "W_ih": id(W_ih), "W_hh": id(W_hh), "W_out": id(W_out)}
         if seq is not None:      # reduced once per sequence (WeightGradSink.end_sequence)
-            seq.dq_steps[ctx.seq_t] = dq      # (a reference, no copy: see _SequenceStage.dq_rows)
+            seq.steps[ctx.seq_t].dq = dq      # (a reference, no copy: see _SequenceStage.dq_rows)
             seq.bwd_steps.append(ctx.seq_t)
-            seq.split, seq.H = ctx.split, H
-            seq.ids = {"Wp": id(Wp), "W_ih": id(W_ih), "W_hh": id(W_hh), "W_out": id(W_out)}
-            gWp = gbp = gWih = gbih = gWhh = gbhh = gWo = gbo = None
+            seq.split, seq.H, seq.ids = ctx.split, H, ids
         elif sink is not None:
-            split = ctx.split
-            sink.weight(("Wp_x", id(Wp)), d_proj, x, lambda g: split("Wp", g, 0))
-            sink.weight(("Wp_h", id(Wp)), d_proj, h, lambda g: split("Wp", g, H))
-            sink.bias(("bp", id(Wp)), d_proj, lambda g: split("bp", g, 0))
-            sink.weight(("W_ih", id(W_ih)), d_gi, inp, lambda g: split("W_ih", g, 0))
-            sink.bias(("b_ih", id(W_ih)), d_gi, lambda g: split("b_ih", g, 0))
-            sink.weight(("W_hh", id(W_hh)), d_gh, h, lambda g: split("W_hh", g, 0))
-            # d_gh == d_gi on the r and z columns: only the n block of b_hh needs its own pass over d_gh
-            sink.bias(("b_hh_n", id(W_hh)), d_gh[:, 2 * H:], lambda g: split("b_hh", g, 2 * H))
-            sink.weight(("W_out", id(W_out)), dq, h2, lambda g: split("W_out", g, 0))
-            sink.bias(("b_out", id(W_out)), dq, lambda g: split("b_out", g, 0))
-            gWp = gbp = gWih = gbih = gWhh = gbhh = gWo = gbo = None
+            sink.step_grads(ctx.split, ids, H, x, h, h2, inp, d_proj, d_gi, d_gh, dq)
         else:
             gWp = th.cat((_wgrad(d_proj, x), _wgrad(d_proj, h)), 1)
             gbp = _colsum(d_proj)
@@ -1674,6 +1558,131 @@ class _TarmacStep(th.autograd.Function):
             gWhh, gbhh = _wgrad(d_gh, h), th.cat((gbih[:2 * H], _colsum(d_gh[:, 2 * H:])))
             gWo, gbo = _wgrad(dq, h2), _colsum(dq)
         return (dx, dh, gWp, gbp, gWih, gbih, gWhh, gbhh, gWo, gbo) + (None,) * 11
+
+
+def _step_dh2(fused_gru, sink, dq, dh2, W_out, N, H):
+    """Backward of the recurrent step, stage 1: the gradient of h', d_hout + dq W_out -> (head, dh2_tot).  head = (dq, W_out): the sum
+    is formed INSIDE the gate kernel (the cell ran fused: its pre-activation sets are what that kernel reads) and dh2_tot is the
+    incoming d_hout alone (None = 0); head = None: dh2_tot is the whole gradient, from a vendor GEMM."""
+    if (fused_gru and H % 4 == 0 and W_out.shape[0] <= 64 and W_out.is_contiguous()
+            and W_out.dtype == th.float32 and W_out.data_ptr() % 16 == 0
+            and (dh2 is None or (dh2.is_contiguous() and dh2.dtype == th.float32 and dh2.shape == (N, H)))):
+        if sink is not None:
+            sink.owned.clear()
+        return (dq, W_out.detach()), dh2
+    if dh2 is None:
+        return None, th.mm(dq, W_out)
+    if (sink is not None and dh2.is_contiguous() and dh2.dtype == th.float32 and dh2.shape == (N, H)
+            and sink.owned.get(dh2.data_ptr()) is not None):
+        # inside the learner's BPTT the incoming d h' is the buffer the NEXT step's backward of this very op
+        # allocated and returned (registered in sink.owned and kept alive there): nobody else holds it, so accumulate
+        # in place instead of copying 33 MB into a fresh output first.  Any other gradient tensor (a hook's,
+        # retain_grad's, one autograd summed from several consumers) lives at another address and is left untouched.
+        sink.owned.clear()
+        return None, dh2.addmm_(dq, W_out)
+    return None, th.addmm(dh2, dq, W_out)
+
+
+def _step_gate_grads(seq, t, fused_gru, gi, gh, h, dh2_tot, head, W_hh):
+    """Stage 2: the gate gradients -> (d_gi, d_gh, dh, rm_g, g4).  seq / t: the staged sequence and the step's slot (None: a step of its
+    own); gi: the saved [N, 4H] pre-activation sets when the cell ran fused, else gi / gh are the two [N, 3H] blocks.  rm_g [N]: the row
+    maxima of d_gi / d_gh where the f16x2 products behind take them (else None); g4 [N, 4H]: the packed buffer [dn_h | dr | dz | dn_i]
+    when the step stores its gate gradients once - d_gi is then its view g4[:, H:] and d_gh is None."""
+    N, H = h.shape
+    rm_g = g4 = None
+    if seq is not None:      # staged sequence: the gate gradients go straight into the time-batched buffers
+        rec = seq.steps[t]
+        G = L.lib().uavgnn_gru_gates_bwd_sum_rows(N, H)
+        # the step's share of db_ih / db_hh comes out of the gate kernel: end_sequence() sums [T1 G, 4H] partials instead of
+        # streaming the [T1 N, 3H] gate gradients twice more
+        sums = seq.slot("gsum", t, 4 * H, rows=G) if G else None
+        if sums is not None and H == 256 and W_hh.stride(1) == 1:
+            if G4 and gemm_h2_supported(seq.slot("g4", t, 4 * H)[:, H:], H, 3 * H):
+                g4 = seq.slot("g4", t, 4 * H)          # ONE buffer [dn_h | dr | dz | dn_i]: the r / z columns are stored once
+            if g4 is not None or gemm_h2_supported(seq.slot("d_gh", t, 3 * H), H, 3 * H):
+                rm_g = seq.slot("rm_g", t, 1).view(N)  # row maxima of d_gi / d_gh for the f16x2 products of stage 3 (and, over the
+                #                                        whole sequence, for the weight gradients)
+        rec.gsum, rec.packed, rec.rm_g = sums is not None, g4 is not None, rm_g is not None
+        if g4 is not None:
+            # packed mode of the gate entry: d_gi == d_gh + H.  d_gi = G[:, H:] in its natural order; `d_gh` is NOT the plain
+            # operand (its column blocks come in the order n, r, z): d h in stage 3 takes it as two sources
+            d_gi, _, dh = _gru_gates_bwd_from_pre(gi, h, dh2_tot, g4[:, H:], g4[:, :3 * H], head=head, sums=sums, rowmax=rm_g)
+            return d_gi, None, dh, rm_g, g4
+        d_gi, d_gh, dh = _gru_gates_bwd_from_pre(gi, h, dh2_tot, seq.slot("d_gi", t, 3 * H), seq.slot("d_gh", t, 3 * H),
+                                                 head=head, sums=sums, rowmax=rm_g)
+    elif fused_gru:
+        d_gi, d_gh, dh = _gru_gates_bwd_from_pre(gi, h, dh2_tot, head=head)      # gi holds the saved pre-activation sets
+    else:
+        d_gi, d_gh, dh = th.empty_like(gi), th.empty_like(gh), th.empty_like(h)
+        with KERNEL_TIMER.span("gru_gates_bwd"):
+            rc = L.lib().uavgnn_gru_gates_bwd(gi.data_ptr(), gh.data_ptr(), h.data_ptr(), dh2_tot.data_ptr(), N, H,
+                                              d_gi.data_ptr(), d_gh.data_ptr(), dh.data_ptr(), L.stream())
+        L.check(rc, "uavgnn_gru_gates_bwd")
+    return d_gi, d_gh, dh, rm_g, g4
+
+
+def _step_input_grads(seq, t, sink, dims, env, dx_out, proj, a_save, Wp, W_ih, W_hh, talk, d_gi, d_gh, dh, rm_g, g4):
+    """Stage 3: the input gradients -> (dx, d_proj); d h += d_gh W_hh is accumulated into `dh` in place.  d c = d_gi W_ih[:, H:], the
+    attention backward (d c -> d_proj) and d x = d_gi W_ih[:, :H] + d_proj Wp[:, :H].  dx_out: where the caller wants d x (the slice of
+    the time-split gradient buffer) or None; talk = (talk_off, talk_src, transpose); rm_g / g4: stage 2's."""
+    M, K = dims
+    N, H = dh.shape
+    # d_inp = d_gi W_ih is [N, H + M]: d x | d c.  When the bf16x3 GEMM has the H-column shape, the two halves are separate
+    # products: d x lands where the caller wants it (the slice of the time-split gradient buffer) and the projection term is
+    # accumulated into it in place - no [N, H] copy in front of the addmm, and 256 of the 320 columns leave the vendor's
+    # 64 x 32-tile solution (134 us) for the matrix-core kernel
+    split_dinp = (M > 0 and W_ih.stride(1) == 1 and gemm_x3_supported(d_gi, H, W_ih.shape[0])
+                  and (dx_out is None or (dx_out.stride(1) == 1 and dx_out.dtype == th.float32)))
+    ld = M + 2 * K
+    d_proj = th.empty((N, ld), dtype=th.float32, device=dh.device) if seq is None else seq.slot("d_proj", t, ld)
+    dx_cat = False
+    if split_dinp:
+        dx = dx_out if dx_out is not None else th.empty((N, H), dtype=th.float32, device=dh.device)
+        # d x = d_gi W_ih[:, :H] + d_proj Wp[:, :H]: ONE product over [d_gi || d_proj] once d_proj exists (behind the attention
+        # backward) instead of a product + an accumulating vendor GEMM that re-reads and re-writes d x (31 us per step)
+        dx_cat = Wp.stride(1) == 1 and gemm_x3_cat_supported(d_gi, d_proj, H)
+        if not dx_cat:
+            _mm_nn(d_gi, W_ih[:, :H], out=dx)
+        if rm_g is not None and M == 64 and gemm_h2_n64_supported(d_gi, M, 3 * H):
+            d_c = gemm_h2_n64(d_gi, W_ih[:, H:], rm_g)                 # [N, M], f16x2 on 128 x 64 tiles
+        else:
+            d_c = th.mm(d_gi, W_ih[:, H:])                             # [N, M]
+        d_c_ptr, d_c_ld = d_c.data_ptr(), M
+    else:
+        d_inp = _mm_nn(d_gi, W_ih)
+        d_c_ptr, d_c_ld = d_inp.data_ptr() + 4 * H, H + M
+    if g4 is not None:
+        # d h += d_gh W_hh over K in the order r, z, n as ever: [G[:, H:3H] || G[:, :H]] [W_hh[:2H]; W_hh[2H:]] (the stacked weight IS
+        # W_hh: the same planes and scales)
+        gemm_h2(g4[:, H:3 * H], W_hh[:2 * H], rm_g, True, out=dh, accumulate=True, a2=g4[:, :H], W2=W_hh[2 * H:])
+    else:
+        _mm_nn(d_gh, W_hh, out=dh, accumulate=True, rowmax=rm_g)
+    if sink is not None:
+        sink.owned.clear()
+        sink.owned[dh.data_ptr()] = dh
+    talk_off, talk_src, transpose = talk
+    _launch_talk_bwd(env, proj.data_ptr() + 4 * M, ld, proj.data_ptr() + 4 * (M + K), ld, proj.data_ptr(), ld,
+                     K, M, talk_off, talk_src, transpose, N, 1.0 / K, a_save, d_c_ptr,
+                     d_c_ld, d_proj.data_ptr() + 4 * M, ld, d_proj.data_ptr() + 4 * (M + K), ld, d_proj.data_ptr(),
+                     ld)
+    if dx_cat and rm_g is not None and gemm_h2_supported(d_gi, H, d_gi.shape[1] + d_proj.shape[1]):
+        # f16x2: the row scale of [d_gi || d_proj] is the larger of the gate kernel's bound and d_proj's own, which the launch takes
+        # itself (96 columns per row, read once more by its workgroups: a microsecond against a 7.8-us pass of uavgnn_row_absmax)
+        if seq is not None:      # kept for the sequence: the column bound of d_proj in the weight gradient dWp (end_sequence)
+            rm_p = seq.slot("rm_p", t, 1).view(N)
+            seq.steps[t].rm_p = True
+        else:
+            rm_p = th.empty(N, dtype=th.float32, device=d_gi.device)
+        gemm_h2(d_gi, W_ih[:, :H], rm_g, True, out=dx, a2=d_proj, W2=Wp[:, :H], rowmax2_out=rm_p)
+    elif dx_cat:
+        gemm_x3_cat(d_gi, d_proj, W_ih[:, :H], Wp[:, :H], dx)
+    elif split_dinp:
+        dx.addmm_(d_proj, Wp[:, :H])                                   # h enters the projections stop-gradded
+    elif dx_out is not None:                                           # slice of the time-split gradient buffer
+        dx = th.addmm(d_inp[:, :H], d_proj, Wp[:, :H], out=dx_out)
+    else:
+        dx = th.addmm(d_inp[:, :H], d_proj, Wp[:, :H])
+    return dx, d_proj
 
 
 def tarmac_step(x, h, g, comm, f_out, stacked=None, dx_out=None):
