@@ -415,6 +415,20 @@ int uavgnn_env_step(const int32_t* int_consts, const double* f64_consts, int B, 
                     int32_t* gt_rb, float* rate_per_gt, double* rate_per_ubs, int32_t* mask_collision, double* reward,
                     float* done, float* obs_gt, float* obs_ubs, float* obs_agent, float* state, uavgnn_stream_t stream);
 
+/* Reset-time placements of the simulator, B environments per launch: initial UBS positions pos_ubs [B,n,2] f64, GT
+ * positions pos_gts [B,M,2] f32 and the initial GT priority permutation prior [B,M] - what uavgnn_env_step(actions = NULL)
+ * consumes - drawn as the reference's maps draw them (envs/mubs_cov/maps.py set_positions of Map, Debug, HotSpot,
+ * DenseHotSpot, DenseHotSpotV2; np.random.permutation at mubs_cov.py:96): UBSs on distinct lattice points, GTs on distinct
+ * lattice points / in a hotspot block / in groups around distinct cells of a hotspot block, GT rows shuffled.  Counter-based
+ * Philox4x32-10: key = seed rng[0], counter = (environment, draw slot, rng[1]); rng is a DEVICE array {seed, resets} (a
+ * captured graph replays with the current counter; the caller advances it), so environment b's placement depends on
+ * (seed, resets, b) only.  fixed_ubs [n,2] f64 / fixed_gts [M,2] f32: the placement of kind `fixed` (NULL otherwise).
+ * n <= 16, M <= 1024, else UAVGNN_EUNSUPPORTED.  int_consts / f64_consts: HOST arrays; their layout, the draw slots and the
+ * sampling rules are in csrc/map_sample.hip. */
+int uavgnn_map_sample(const int32_t* int_consts, const double* f64_consts, int B, const long long* rng,
+                      const double* fixed_ubs, const float* fixed_gts, double* pos_ubs, float* pos_gts, int32_t* prior,
+                      uavgnn_stream_t stream);
+
 /* The four construction passes above + the three prefix sums in ONE launch for small batches (B n <=
  * uavgnn_build_graph_small_max_agents() = 4096 agents; reference: env_wrappers.py:65-89,:122-154 for B environments): seen_off /
  * near_off / talk_off [B n + 1], graph_off [B + 1] and the compacted x_gt / x_ubs / talk_src / talk_eid (allocated by the

@@ -10,15 +10,23 @@ tensor-native replay consume, so a rollout never leaves the GPU: simulator -> gr
     obs, reward, done, info = env.step(actions)        # actions [B, n] int64 on the device
     g = env.graph()                                    # HeteroBatch of the current observations (f1)
 
-Initial positions and the initial GT priority permutation are INPUTS (the reference draws them from Python's / NumPy's
-global generators in ``Map.set_positions`` and ``reset``); ``reset()`` without arguments places UBSs and GTs uniformly.
+Initial positions and the initial GT priority permutation are INPUTS of ``reset`` (the reference draws them from Python's /
+NumPy's global generators in ``Map.set_positions`` and ``reset``); ``reset()`` without arguments places UBSs and GTs uniformly.
+
+The reference's own maps and placements: ``MAPS`` holds its eight registered maps (maps.py:138-151) as ``MapSpec``s, and
+
+    env = BatchedUbsCoverageEnv.from_map("8ubs", B=4096, seed=0)
+    obs = env.reset_from_map()                         # placements drawn on the device: ONE launch (csrc/map_sample.hip)
+
+draws what ``Map.set_positions`` + ``np.random.permutation`` draw - UBSs on distinct lattice points, GTs in a shuffled hotspot
+- from a counter-based generator keyed by a device ``{seed, resets}`` pair, so the reset is reproducible and graph-capturable.
 """
 from __future__ import annotations
 
 import ctypes
 import dataclasses
 import math
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple, Union
 
 import numpy as np
 import torch as th
@@ -81,6 +89,87 @@ class MapParams:
         return np.ascontiguousarray(np.concatenate((np.zeros((1, 2)), np.kron(amounts, dirs))))
 
 
+KINDS = ("uniform_lattice", "fixed", "hotspot", "dense_hotspot", "dense_hotspot_v2")
+
+
+@dataclasses.dataclass
+class MapSpec:
+    """A reference map: the parameters it splats onto the env + how ``set_positions`` places UBSs and GTs.
+
+    kind             reference                    integers
+    uniform_lattice  Map.set_positions :31-35     - (UBSs and GTs on distinct points of the 1 m lattice)
+    fixed            Debug :47-50                 fixed_ubs [n,2], fixed_gts [M,2]
+    hotspot          HotSpot :64-75               min_dist (lattice pitch, m)
+    dense_hotspot    DenseHotSpot :97-113         min_dist, n_grps, gts_per_grp
+    dense_hotspot_v2 DenseHotSpotV2 :125-132      ubs_pitch (UBS lattice pitch, m), radius_spot (half the hotspot's side, m)
+    """
+    params: MapParams
+    kind: str
+    min_dist: int = 200
+    n_grps: int = 0
+    gts_per_grp: int = 0
+    ubs_pitch: int = 100
+    radius_spot: int = 400
+    fixed_ubs: Optional[tuple] = None
+    fixed_gts: Optional[tuple] = None
+
+    def sampler_consts(self) -> Tuple[list, list]:
+        """(int_consts, f64_consts) of uavgnn_map_sample (layout: csrc/map_sample.hip), by the reference's own integer arithmetic."""
+        p, kind = self.params, KINDS.index(self.kind)
+        n, M, rng_pos = p.n_ubs, p.n_gts, p.range_pos
+        L_u, L_s, r, n_picks, gpg, origin = int(rng_pos), 1, 1, 0, 1, 0
+        pitch_u, pitch_s, pitch_c, spread = 1.0, 0.0, 0.0, 0.0
+        if self.kind in ("hotspot", "dense_hotspot"):
+            n_picks, gpg = (M, 1) if self.kind == "hotspot" else (self.n_grps, self.gts_per_grp)
+            if n_picks * gpg != M:
+                raise ValueError(f"{self.kind}: n_grps x gts_per_grp = {n_picks} x {gpg} is not n_gts = {M}")
+            r = 1
+            while r * r < n_picks:                                                   # maps.py:68-69 / :101-102
+                r += 1
+            L_u = int(rng_pos // self.min_dist)
+            L_s = int(rng_pos // self.min_dist // r)
+            pitch_u, pitch_s, pitch_c = float(self.min_dist), float(self.min_dist * r), float(self.min_dist)
+            spread = 0.0 if self.kind == "hotspot" else float(p.r_cov)
+        elif self.kind == "dense_hotspot_v2":
+            L_u, pitch_u = int(rng_pos // self.ubs_pitch), float(self.ubs_pitch)
+            L_s, origin, pitch_s = int(rng_pos // self.radius_spot) - 1, 1, float(self.radius_spot)  # arange(1, range_pos // 400)
+            spread = float(2 * self.radius_spot)
+        return [kind, n, M, L_u, L_s, r, n_picks, gpg, origin], [float(rng_pos), pitch_u, pitch_s, pitch_c, spread]
+
+
+def _hotspot(**kw) -> MapSpec:                                                           # maps.py:59-62
+    p = dict(range_pos=2000.0, episode_limit=40, dt=20.0, n_ubs=4, n_gts=4, r_cov=100.0, n_rbs=1, r_sns=200.0, r_comm=math.inf,
+             vels=(5.0, 10.0), n_dirs=4, reward_scale_rate=10.0)
+    p.update(kw)
+    return MapSpec(MapParams(**p), "hotspot")
+
+
+def _dense_hotspot(n_grps=10, gts_per_grp=5, **kw) -> MapSpec:                            # maps.py:88-95
+    p = dict(range_pos=6000.0, episode_limit=50, dt=40.0, n_ubs=4, n_gts=n_grps * gts_per_grp, r_cov=100.0, n_rbs=5, r_sns=400.0,
+             r_comm=math.inf, vels=(5.0, 10.0), n_dirs=4, reward_scale_rate=10.0)
+    p.update(kw)
+    return MapSpec(MapParams(**p), "dense_hotspot", n_grps=n_grps, gts_per_grp=gts_per_grp)
+
+
+def dense_hotspot_v2(**overrides) -> MapSpec:
+    """The reference's unregistered hard mode ``DenseHotSpotV2`` (maps.py:117-132); overrides: ``MapParams`` fields."""
+    p = dict(range_pos=6000.0, episode_limit=100, dt=10.0, n_ubs=4, n_gts=100, r_cov=100.0, n_rbs=10, r_sns=400.0, r_comm=math.inf,
+             vels=(5.0, 10.0), n_dirs=4, reward_scale_rate=10.0)
+    p.update(overrides)
+    return MapSpec(MapParams(**p), "dense_hotspot_v2")
+
+
+# the reference's registry (maps.py:138-151)
+MAPS: Dict[str, MapSpec] = {
+    "test": MapSpec(MapParams(n_ubs=1, n_gts=1), "uniform_lattice"),                                              # Map()
+    "debug": MapSpec(MapParams(n_ubs=3, n_gts=4, range_pos=1000.0, episode_limit=10, r_sns=300.0), "fixed",       # Debug()
+                     fixed_ubs=((300.0, 300.0), (800.0, 200.0), (800.0, 900.0)),
+                     fixed_gts=((300.0, 400.0), (400.0, 200.0), (300.0, 100.0), (600.0, 900.0))),
+    "inf": _hotspot(), "r400": _hotspot(r_comm=400.0), "r800": _hotspot(r_comm=800.0),                            # experiment 2
+    "4ubs": _dense_hotspot(n_ubs=4), "6ubs": _dense_hotspot(n_ubs=6), "8ubs": _dense_hotspot(n_ubs=8),            # experiment 3
+}
+
+
 class BatchedUbsCoverageEnv:
     def __init__(self, p: MapParams, B: int, device="cuda", max_rate: Optional[float] = None):
         self.p, self.B, self.device = p, B, th.device(device)
@@ -110,8 +199,33 @@ class BatchedUbsCoverageEnv:
                         obs_gt=th.zeros(B, n, M, Sg, **f32), obs_ubs=th.zeros(B, n, max(n - 1, 0), 3, **f32),
                         obs_agent=th.zeros(B, n, 2, **f32), state=th.zeros(B, self.state_dim, **f32))
         self.ep_ret = th.zeros(B, **f64)
+        self.spec: Optional[MapSpec] = None                  # set by from_map: the placement sampler's map
+        self.map_rng: Optional[th.Tensor] = None             # device int64 {seed, resets} of the placement sampler
 
-    # ---- the one kernel ---------------------------------------------------------------------------------------------
+    @classmethod
+    def from_map(cls, map_id_or_spec: Union[str, MapSpec], B: int, device="cuda", seed: Optional[int] = None):
+        """Environment of a registered map (``MAPS``) or of a ``MapSpec``, with the map's placement sampler attached
+        (``reset_from_map`` / ``sample_positions``).  seed: the sampler's key (None: drawn from torch's default generator, so
+        ``torch.manual_seed`` reproduces a run)."""
+        spec = MAPS[map_id_or_spec] if isinstance(map_id_or_spec, str) else map_id_or_spec
+        if spec.kind not in KINDS:
+            raise ValueError(f"unknown placement kind {spec.kind!r}: one of {KINDS}")
+        env = cls(spec.params, B, device)
+        ic, fc = spec.sampler_consts()
+        env.spec = spec
+        env._map_ic, env._map_fc = (ctypes.c_int32 * len(ic))(*ic), (ctypes.c_double * len(fc))(*fc)
+        env._map_fixed = (None, None)
+        if spec.kind == "fixed":
+            env._map_fixed = (th.as_tensor(spec.fixed_ubs, dtype=th.float64, device=env.device).reshape(-1, 2).contiguous(),
+                              th.as_tensor(spec.fixed_gts, dtype=th.float32, device=env.device).reshape(-1, 2).contiguous())
+            if env._map_fixed[0].shape[0] != env.n_agents or env._map_fixed[1].shape[0] != env.n_gts:
+                raise ValueError("fixed placement: fixed_ubs / fixed_gts must hold n_ubs / n_gts points")
+        if seed is None:
+            seed = int(th.randint(0, 2 ** 62, (1,)).item())
+        env.map_rng = th.tensor([int(seed), 0], dtype=th.int64, device=env.device)
+        return env
+
+    # ---- the two kernels ---------------------------------------------------------------------------------------------
     def _launch(self, actions: Optional[th.Tensor]):
         L.require_gpu(self.pos_ubs, actions)
         o = self.out
@@ -154,6 +268,35 @@ class BatchedUbsCoverageEnv:
         for t_ in (self.avg_rate, self.t, self.run_f32, self.n_colls, self.ep_ret):
             t_.zero_()
         self._launch(None)                                     # UBSs serve the GTs at the initial positions (:98)
+        return self.observations()
+
+    def _sample_into(self, pos_ubs: th.Tensor, pos_gts: th.Tensor, prior: th.Tensor):
+        """One uavgnn_map_sample launch at the current {seed, resets}; then resets += 1 on the device (capturable)."""
+        if self.spec is None:
+            raise L.UavGnnError("this environment has no map: build it with BatchedUbsCoverageEnv.from_map(...)")
+        L.require_gpu(pos_ubs, pos_gts, prior, self.map_rng)
+        fu, fg = self._map_fixed
+        L.check(L.lib().uavgnn_map_sample(self._map_ic, self._map_fc, self.B, self.map_rng.data_ptr(), L.ptr(fu), L.ptr(fg),
+                                          pos_ubs.data_ptr(), pos_gts.data_ptr(), prior.data_ptr(), L.stream()),
+                "uavgnn_map_sample")
+        self.map_rng[1:].add_(1)
+
+    def sample_positions(self):
+        """(pos_ubs [B,n,2] f64, pos_gts [B,M,2] f32, prior [B,M] i32) as the map's ``set_positions`` + the reset's
+        ``np.random.permutation`` draw them (maps.py, mubs_cov.py:94-96), in fresh tensors; advances the reset counter."""
+        B, n, M, dev = self.B, self.n_agents, self.n_gts, self.device
+        out = (th.empty(B, n, 2, dtype=th.float64, device=dev), th.empty(B, M, 2, dtype=th.float32, device=dev),
+               th.empty(B, M, dtype=th.int32, device=dev))
+        self._sample_into(*out)
+        return out
+
+    def reset_from_map(self):
+        """mubs_cov.py:86-102 with the map's own placements: the sampler launch (into the state buffers), the running state zeroed as
+        ``reset`` zeroes it, the reset-time transmission launch.  No host synchronisation, fixed addresses: capturable."""
+        self._sample_into(self.pos_ubs, self.pos_gts, self.prior)
+        for t_ in (self.avg_rate, self.t, self.run_f32, self.n_colls, self.ep_ret):
+            t_.zero_()
+        self._launch(None)
         return self.observations()
 
     def step(self, actions: th.Tensor):
