@@ -7,13 +7,46 @@
     TIME=1 ... 20 extra launches of each entry (for rocprofv3 --kernel-trace)
     UAVGNN_K1_BWD_MFMA=0 sends every destination through the packed-FMA kernel.
 
+    python tools/k1_bwd_repro.py --deg 80 [--n 1671168] [--launches 20]      timing run: the data is made on the GPU, only
+    uavgnn_gatv2_bwd is launched (for rocprofv3 --kernel-trace); --deg D or LO..HI (uniform), e.g. 80, 96, 16..52.  The A/B
+    switches of the launcher (UAVGNN_K1_BWD_RESIDENT / _PREFETCH / _HALFTRIP) select the kernel.
+
 This is the script that located the gfx950 packed-fp32 / bf16-MFMA hazard (tools/ubench/mfma_pk_hazard.hip):
 CASES are (destinations, min degree, max degree).
 """
-import sys, os
-sys.path.insert(0, "/root/repo")
+import argparse, sys, os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch as th
 from uav_bs_ctrl_amd import _lib as L
+ap = argparse.ArgumentParser()
+ap.add_argument("--deg", help="timing run at this in-degree: D, or LO..HI for a uniform mix")
+ap.add_argument("--n", type=int, default=51 * 32768, help="destinations of the timing run (default: the bench's 51 x 32768)")
+ap.add_argument("--launches", type=int, default=20)
+args = ap.parse_args()
+def timing_run(lo, hi, N, launches):
+    dev = "cuda"; gen = th.Generator(device=dev).manual_seed(11); H = 256
+    deg = th.randint(lo, hi + 1, (N,), generator=gen, device=dev)
+    off = th.zeros(N + 1, dtype=th.int64, device=dev); off[1:] = th.cumsum(deg, 0); E = int(off[-1]); offd = off.to(th.int32)
+    x_src = th.rand(E, 4, generator=gen, device=dev) * 2 - 1; x_dst = th.rand(N, 2, generator=gen, device=dev)
+    prm = [0.5 * th.randn(s, generator=gen, device=dev) for s in ((H, 4), (H,), (H, 2), (H,), (H,), (H, 2), (H,))]
+    out = th.empty(N, H, device=dev); a_save = th.empty(E, 4, device=dev); lib, st = L.lib(), L.stream()
+    assert lib.uavgnn_gatv2_fwd(x_src.data_ptr(), E, 4, x_dst.data_ptr(), 2, offd.data_ptr(), None, N, *[t.data_ptr() for t in prm], 4, 64, 0.2, out.data_ptr(), H, a_save.data_ptr(), st) == 0
+    d_out = th.randn(N, H, generator=gen, device=dev)
+    wsb = lib.uavgnn_gatv2_bwd_workspace_bytes(4, H); ws = th.empty(wsb // 4, device=dev)
+    g = [th.empty_like(t) for t in prm]
+    ev = [th.cuda.Event(enable_timing=True) for _ in range(launches + 1)]
+    for i in range(launches + 1):
+        ev[i].record()
+        if i < launches:
+            assert lib.uavgnn_gatv2_bwd(x_src.data_ptr(), E, 4, x_dst.data_ptr(), 2, offd.data_ptr(), None, N, *[t.data_ptr() for t in prm[:5]], 4, 64, 0.2, out.data_ptr(), d_out.data_ptr(), H, a_save.data_ptr(), *[t.data_ptr() for t in g], ws.data_ptr(), wsb, st) == 0
+    th.cuda.synchronize()
+    ms = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(2, launches))   # the first two launches are warm-up
+    print(f"k1_bwd N {N} deg {lo}..{hi} E {E}: whole backward (3 kernels) per launch ms min {ms[0]:.3f} p50 {ms[len(ms) // 2]:.3f} max {ms[-1]:.3f}"
+          f" ; checksum {float(sum(t.double().sum() for t in g)):.9e}")
+if args.deg:
+    lo, _, hi = args.deg.partition("..")
+    timing_run(int(lo), int(hi or lo), args.n, args.launches)
+    sys.exit(0)
 def case(N, lo, hi, seed):
     gen = th.Generator().manual_seed(seed)
     deg = th.randint(lo, hi + 1, (N,), generator=gen)

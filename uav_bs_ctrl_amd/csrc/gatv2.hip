@@ -29,7 +29,8 @@ int gatv2_bwd_mfma_launch(const float* x_src, const float* x_dst, const int32_t*
                           const float* out, const float* d_out, int ld_out, const float* a_save, float* partial,
                           int onepass_max_deg, int grid, hipStream_t st);
 // defined in gatv2_bwd_mfma.hip: launches gatv2_bwd_resident_kernel (the same class, matrix-core accumulators resident over all
-// destinations of a wavefront); same arguments and partial-row layout, a_save rows 16-byte aligned
+// destinations of a wavefront); same arguments and partial-row layout, a_save rows 16-byte aligned.  Reads its own A/B switches
+// at every call: UAVGNN_K1_BWD_LEAN=0, UAVGNN_K1_BWD_HALFTRIP=0
 int gatv2_bwd_resident_launch(const float* x_src, const float* x_dst, const int32_t* seg_off, const int32_t* dst_order, int N,
                               const float* W_s, const float* b_s, const float* W_d, const float* b_d, const float* attn, float slope,
                               const float* out, const float* d_out, int ld_out, const float* a_save, float* partial,

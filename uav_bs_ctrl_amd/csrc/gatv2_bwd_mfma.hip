@@ -12,6 +12,8 @@
 // destination now and then (bit-irreproducible gradients).  tools/isa_audit.py (tests/test_isa_audit.py) checks the shipped
 // library for the pattern: no kernel with 16-bit-operand MFMAs may hold such an instruction.
 #define UAVGNN_GATV2_BWD_MFMA_TU 1
+#include <type_traits>
+
 #include "gatv2.hip"
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -52,6 +54,26 @@ __device__ __forceinline__ void wave_totals16(const float (&v)[16], float (&t)[4
   }
 }
 
+// k1_split of two values at once, packed the way the V operand wants them: (a_t | b_t << 16) of the three terms.  One conversion
+// instruction per term converts both values (k1_split converts each value into both halves and the caller merges two words);
+// each half is the same round-to-nearest conversion, the same bits.
+__device__ __forceinline__ K1Split k1_split_pair(float a, float b) {
+  K1Split s;
+  s.h1 = __builtin_bit_cast(unsigned, __builtin_convertvector(k1_f32x2{a, b}, k1_bf16x2));
+  const float a1 = a - __uint_as_float(s.h1 << 16), b1 = b - __uint_as_float(s.h1 & 0xffff0000u);
+  s.h2 = __builtin_bit_cast(unsigned, __builtin_convertvector(k1_f32x2{a1, b1}, k1_bf16x2));
+  const float a2 = a1 - __uint_as_float(s.h2 << 16), b2 = b1 - __uint_as_float(s.h2 & 0xffff0000u);
+  s.h3 = __builtin_bit_cast(unsigned, __builtin_convertvector(k1_f32x2{a2, b2}, k1_bf16x2));
+  return s;
+}
+
+// LEAN: fewer instructions per destination (the kernel issues ~2 200 per 80-edge destination and its time is their issue time,
+// DESIGN.md section 5): the V operands of two edges split by k1_split_pair; the W operand of a channel tile read as three words +
+// the bias word instead of a 16-byte read whose last word is then overwritten; the S1 rows zeroed by DPP moves, their sign put
+// on behind the swaps.
+// HT: a last trip of at most 16 edges runs on its first score tile only.  false / false: the kernel as first shipped; same bits
+// out of all four.
+template <bool LEAN, bool HT>
 __global__ __launch_bounds__(kThreads, UAVGNN_BWD_OCC) void gatv2_bwd_resident_kernel(
     const float* __restrict__ x_src, const float* __restrict__ x_dst, const int32_t* __restrict__ seg_off,
     const int32_t* __restrict__ dst_order, int N,
@@ -237,11 +259,35 @@ __global__ __launch_bounds__(kThreads, UAVGNN_BWD_OCC) void gatv2_bwd_resident_k
     const bwd_f32x4 czero = {0.f, 0.f, 0.f, 0.f};
     unsigned k_sign = 0x80008000u, k_one = 0x3F803F80u;
     asm volatile("" : "+v"(k_sign), "+v"(k_one));
-    for (int tp = 0; 32 * tp < deg; ++tp) {
-      {
+    // one trip: 32 edges as two 16-edge score tiles and one K = 32 accumulation per channel tile.  HALF (the last trip when at most
+    // 16 edges are left): the second tile's edges are padding - no score products, no sign words and no V operands for them;
+    // their K positions of the accumulation take zeros on both sides (the V words of tile 1 in LDS are the previous trip's).
+    auto trip = [&](const int tp, auto half_c) {
+      constexpr bool HALF = decltype(half_c)::value;
+      const float* const et = ew + 32 * tp * ES;   // slot 32 tp
+      if constexpr (HALF) {   // lane (edge i16, head h): one edge's half-words
+        int ln = lane;   // opaque: this trip's addresses are worked out here, not kept in registers over the whole kernel
+        asm volatile("" : "+v"(ln));
+        const int i16 = ln & 15, h = ln >> 4;
+        const float* er = et + i16 * ES;
+        const bwd_f32x4 xa = *reinterpret_cast<const bwd_f32x4*>(er);
+        const float da = er[FS + h];
+        const float va[5] = {da, da * xa[0], da * xa[1], da * xa[2], da * xa[3]};
+        const int skew = (i16 >> 2) + 4 * h;
+        unsigned short* dst = reinterpret_cast<unsigned short*>(reinterpret_cast<unsigned*>(vw) + (h * kWave + (i16 >> 2) * 16) * 4 +
+                                                                ((i16 & 3) >> 1)) + (i16 & 1);
+#pragma unroll
+        for (int f = 0; f < 5; ++f) {
+          const K1Split sa = k1_split(va[f]);
+          const int r0 = f == 0 ? 0 : 2 + f, dr = f == 0 ? 1 : 4;
+          dst[((r0 + 0 * dr + skew) & 15) * 8] = static_cast<unsigned short>(sa.h1);
+          dst[((r0 + 1 * dr + skew) & 15) * 8] = static_cast<unsigned short>(sa.h2);
+          dst[((r0 + 2 * dr + skew) & 15) * 8] = static_cast<unsigned short>(sa.h3);
+        }
+      } else {
         const int ep = lane & 15, h = lane >> 4;
         const int e_a = 2 * ep, i16 = e_a & 15;
-        const float* er = ew + (32 * tp + e_a) * ES;
+        const float* er = et + e_a * ES;
         const bwd_f32x4 xa = *reinterpret_cast<const bwd_f32x4*>(er), xb = *reinterpret_cast<const bwd_f32x4*>(er + ES);
         const float da = er[FS + h], db = er[ES + FS + h];
         const float va[5] = {da, da * xa[0], da * xa[1], da * xa[2], da * xa[3]};
@@ -250,29 +296,48 @@ __global__ __launch_bounds__(kThreads, UAVGNN_BWD_OCC) void gatv2_bwd_resident_k
         unsigned* dst = reinterpret_cast<unsigned*>(vw) + (h * kWave + (i16 >> 2) * 16) * 4 + (((i16 & 3) + 4 * (e_a >> 4)) >> 1);
 #pragma unroll
         for (int f = 0; f < 5; ++f) {   // row of term tt of value f: tt (f = 0, the S1 rows) or 3 + 4 tt + f - 1 (S2)
-          const K1Split sa = k1_split(va[f]), sb2 = k1_split(vb[f]);
           const int r0 = f == 0 ? 0 : 2 + f, dr = f == 0 ? 1 : 4;
-          dst[((r0 + 0 * dr + skew) & 15) * 4] = (sa.h1 & 0xffffu) | (sb2.h1 & 0xffff0000u);
-          dst[((r0 + 1 * dr + skew) & 15) * 4] = (sa.h2 & 0xffffu) | (sb2.h2 & 0xffff0000u);
-          dst[((r0 + 2 * dr + skew) & 15) * 4] = (sa.h3 & 0xffffu) | (sb2.h3 & 0xffff0000u);
+          if constexpr (LEAN) {
+            const K1Split sp = k1_split_pair(va[f], vb[f]);
+            dst[((r0 + 0 * dr + skew) & 15) * 4] = sp.h1;
+            dst[((r0 + 1 * dr + skew) & 15) * 4] = sp.h2;
+            dst[((r0 + 2 * dr + skew) & 15) * 4] = sp.h3;
+          } else {
+            const K1Split sa = k1_split(va[f]), sb2 = k1_split(vb[f]);
+            dst[((r0 + 0 * dr + skew) & 15) * 4] = (sa.h1 & 0xffffu) | (sb2.h1 & 0xffff0000u);
+            dst[((r0 + 1 * dr + skew) & 15) * 4] = (sa.h2 & 0xffffu) | (sb2.h2 & 0xffff0000u);
+            dst[((r0 + 2 * dr + skew) & 15) * 4] = (sa.h3 & 0xffffu) | (sb2.h3 & 0xffff0000u);
+          }
         }
       }
-      k1_bf16x8 xop[2];
+      constexpr int NT = HALF ? 1 : 2;
+      k1_bf16x8 xop[NT];
 #pragma unroll
-      for (int tt = 0; tt < 2; ++tt) xop[tt] = k1_b_operand(ew[(32 * tp + 16 * tt + j16) * ES + g4], 0x3F803F80u);
+      for (int tt = 0; tt < NT; ++tt) xop[tt] = k1_b_operand(et[(16 * tt + j16) * ES + g4], 0x3F803F80u);
       wave_sync_lds();
-      k1_u32x4 vop = vw[16 * g4 + ((j16 + g4) & 15)], vop_n = vw[kWave + 16 * g4 + ((j16 + g4 + 4) & 15)];
+      auto v_operand = [&](const int i) {
+        k1_u32x4 v = vw[i];
+        if constexpr (HALF) v[2] = v[3] = 0u;
+        return v;
+      };
+      k1_u32x4 vop = v_operand(16 * g4 + ((j16 + g4) & 15)), vop_n = v_operand(kWave + 16 * g4 + ((j16 + g4 + 4) & 15));
       auto w_operand = [&](const int ct_) {
+        if constexpr (LEAN) {   // three words + the bias word into four registers of their own: a 16-byte read whose last word
+          // is then overwritten makes the second read wait for the first (a full LDS round trip per channel tile)
+          const unsigned* wp = reinterpret_cast<const unsigned*>(sWop + ct_ * kWave + lane);
+          const uint2 w01 = *reinterpret_cast<const uint2*>(wp);
+          return __builtin_bit_cast(k1_bf16x8, k1_u32x4{w01.x, w01.y, wp[2], cwl[ct_ * 32]});
+        }
         k1_u32x4 w = sWop[ct_ * kWave + lane];
         w[3] = cwl[ct_ * 32];
         return __builtin_bit_cast(k1_bf16x8, w);
       };
       k1_bf16x8 w_nn = w_operand(1);
-      bwd_f32x4 d0, d1;
+      bwd_f32x4 d0, d1 = czero;
       {
         const k1_bf16x8 w0 = w_operand(0);
         d0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xop[0], w0, czero, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xop[1], w0, czero, 0, 0, 0);
+        if constexpr (!HALF) d1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xop[NT - 1], w0, czero, 0, 0, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -280,45 +345,58 @@ __global__ __launch_bounds__(kThreads, UAVGNN_BWD_OCC) void gatv2_bwd_resident_k
         bwd_f32x4 e0_ = d0, e1_ = d1;
         if (ct + 1 < CT) {
           e0_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xop[0], w_nn, czero, 0, 0, 0);
-          e1_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xop[1], w_nn, czero, 0, 0, 0);
+          if constexpr (!HALF) e1_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xop[NT - 1], w_nn, czero, 0, 0, 0);
           if (ct + 2 < CT) w_nn = w_operand(ct + 2);
           __builtin_amdgcn_sched_barrier(0);
         }
-        k1_u32x4 sg;
+        k1_u32x4 sg = {0u, 0u, 0u, 0u};
 #pragma unroll
         for (int q = 0; q < 2; ++q) {   // d = -(z + c): the sign bits of two edges' values side by side over 1.0
           const unsigned p0 = __builtin_amdgcn_perm(__float_as_uint(d0[2 * q + 1]), __float_as_uint(d0[2 * q]), 0x07060302u);
-          const unsigned p1 = __builtin_amdgcn_perm(__float_as_uint(d1[2 * q + 1]), __float_as_uint(d1[2 * q]), 0x07060302u);
           sg[q] = (p0 & k_sign) | (k_one & ~k_sign);
-          sg[2 + q] = (p1 & k_sign) | (k_one & ~k_sign);
+          if constexpr (!HALF) {
+            const unsigned p1 = __builtin_amdgcn_perm(__float_as_uint(d1[2 * q + 1]), __float_as_uint(d1[2 * q]), 0x07060302u);
+            sg[2 + q] = (p1 & k_sign) | (k_one & ~k_sign);
+          }
         }
         acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(k1_bf16x8, vop), __builtin_bit_cast(k1_bf16x8, sg),
                                                           acc[ct], 0, 0, 0);
         if ((ct & 3) == 3 && ct + 1 < CT) {
           vop = vop_n;
-          if (ct + 5 < CT) vop_n = vw[((ct + 5) >> 2) * kWave + 16 * g4 + ((j16 + g4 + 4 * ((ct + 5) >> 2)) & 15)];
+          if (ct + 5 < CT) vop_n = v_operand(((ct + 5) >> 2) * kWave + 16 * g4 + ((j16 + g4 + 4 * ((ct + 5) >> 2)) & 15));
         }
         __builtin_amdgcn_sched_barrier(0);
         d0 = e0_;
         d1 = e1_;
       }
       wave_sync_lds();
+    };
+    {
+      int tp = 0;
+      for (; 32 * tp + (HT ? 16 : 0) < deg; ++tp) trip(tp, std::false_type{});
+      if (HT && 32 * tp < deg) trip(tp, std::true_type{});
     }
     // ---- S1 of this destination: rows 0..2 of every tile (lanes 0..15), then zeroed; tile 4 k + r -> row r of head k ---------
     float s1[CT];
     const bool s1_lane = lane < 16;
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
-      s1[ct] = -((acc[ct][0] + acc[ct][1]) + acc[ct][2]);
+      const float sum = (acc[ct][0] + acc[ct][1]) + acc[ct][2];
+      s1[ct] = LEAN ? sum : -sum;   // LEAN: the sign goes on behind the swaps (4 values, not 16)
 #pragma unroll
-      for (int i = 0; i < 3; ++i) acc[ct][i] = s1_lane ? 0.f : acc[ct][i];
+      for (int i = 0; i < 3; ++i) {
+        if constexpr (LEAN)   // a DPP move that writes row 0 (lanes 0..15) only, in place: the select drags ~40 register copies behind it
+          acc[ct][i] = __uint_as_float(__builtin_amdgcn_update_dpp(__float_as_uint(acc[ct][i]), 0u, 0xE4, 0x1, 0xf, false));
+        else
+          acc[ct][i] = s1_lane ? 0.f : acc[ct][i];
+      }
     }
 #pragma unroll
     for (int j = 0; j < J; ++j) {
       const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(s1[4 * j]), __float_as_uint(s1[4 * j + 1]), false, false);
       const auto q = __builtin_amdgcn_permlane16_swap(__float_as_uint(s1[4 * j + 2]), __float_as_uint(s1[4 * j + 3]), false, false);
       const auto s = __builtin_amdgcn_permlane32_swap(r[0], q[0], false, false);
-      const float S1 = __uint_as_float(s[0]);   // channel lane + 64 j
+      const float S1 = LEAN ? -__uint_as_float(s[0]) : __uint_as_float(s[0]);   // channel lane + 64 j
       sS1[j] += S1;
       sX0[j] = fmaf(xv0, S1, sX0[j]);
       sX1[j] = fmaf(xv1, S1, sX1[j]);
@@ -367,6 +445,8 @@ __global__ __launch_bounds__(kThreads, UAVGNN_BWD_OCC) void gatv2_bwd_resident_k
   float abs_[J], aWd0[J], aWd1[J], abd[J], aatt[J];
   {
     constexpr int kCvLd = 20;
+    int le = lane;   // the indices of this once-per-wavefront block are made here, not carried (spilled) through the loops above
+    if constexpr (HT) asm volatile("" : "+v"(le));
     float* __restrict__ cv = ew;
 #pragma unroll
     for (int k = 0; k < NH; ++k) {
@@ -380,7 +460,7 @@ __global__ __launch_bounds__(kThreads, UAVGNN_BWD_OCC) void gatv2_bwd_resident_k
         r[4 * q] = t4[0]; r[4 * q + 1] = t4[1]; r[4 * q + 2] = t4[2]; r[4 * q + 3] = t4[3];
       }
       wave_sync_lds();
-      const float att = attn[lane + kWave * k];
+      const float att = attn[le + kWave * k];
       float wS2 = 0.f, wP = 0.f;
 #pragma unroll
       for (int f = 0; f < FS; ++f) {
@@ -440,8 +520,21 @@ int gatv2_bwd_resident_launch(const float* x_src, const float* x_dst, const int3
                               const float* out, const float* d_out, int ld_out, const float* a_save, float* partial,
                               int onepass_max_deg, int grid, hipStream_t st) {
   if (onepass_max_deg > 2 * kWave) return UAVGNN_EINVAL;   // two staged 64-edge chunks per destination
-  hipLaunchKernelGGL(gatv2_bwd_resident_kernel, dim3(grid), dim3(kThreads), 0, st, x_src, x_dst, seg_off, dst_order, N, W_s, b_s,
-                     W_d, b_d, attn, slope, out, d_out, ld_out, a_save, partial, onepass_max_deg);
+  // A/B switches, read at every call like UAVGNN_K1_BWD_RESIDENT: UAVGNN_K1_BWD_LEAN=0 and UAVGNN_K1_BWD_HALFTRIP=0 (see the
+  // kernel's template parameters; both 0: the kernel as first shipped; same bits out)
+  auto off = [](const char* name) {
+    const char* e = getenv(name);
+    return e && e[0] == '0';
+  };
+  const bool lean = !off("UAVGNN_K1_BWD_LEAN"), ht = !off("UAVGNN_K1_BWD_HALFTRIP");
+#define UAVGNN_RESIDENT_LAUNCH(LEANV, HTV)                                                                                          \
+  hipLaunchKernelGGL((gatv2_bwd_resident_kernel<LEANV, HTV>), dim3(grid), dim3(kThreads), 0, st, x_src, x_dst, seg_off, dst_order, \
+                     N, W_s, b_s, W_d, b_d, attn, slope, out, d_out, ld_out, a_save, partial, onepass_max_deg)
+  if (lean && ht) UAVGNN_RESIDENT_LAUNCH(true, true);
+  else if (lean) UAVGNN_RESIDENT_LAUNCH(true, false);
+  else if (ht) UAVGNN_RESIDENT_LAUNCH(false, true);
+  else UAVGNN_RESIDENT_LAUNCH(false, false);
+#undef UAVGNN_RESIDENT_LAUNCH
   return launch_status();
 }
 }  // namespace uavgnn
