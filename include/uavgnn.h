@@ -429,6 +429,31 @@ int uavgnn_map_sample(const int32_t* int_consts, const double* f64_consts, int B
                       const double* fixed_ubs, const float* fixed_gts, double* pos_ubs, float* pos_gts, int32_t* prior,
                       uavgnn_stream_t stream);
 
+/* Batched simulator step of the single-UBS coverage environment of experiment 1, B independent environments per launch
+ * (reference: envs/subs_cov/subs_cov.py:113-133 step, :135-157 _transmit_data, :159-171 get_obs, :186-191 reward and
+ * termination; envs/common.py:19-25 Jain index, :49-59 air-to-ground channel gain).  actions [B] int64 or NULL (the reset-time
+ * transmission: no move, t stays as it is).  In/out per environment: pos_ubs [B,2] f64, prior [B,M] (GT priorities used by
+ * this step -> the stable argsort of the new averages), avg_rate [B,M], t [B], run_f64 [B,4] = {total throughput, average
+ * global utility, Jain index, global utility}.  In: pos_gts [B,M,2], avail_moves [A,2] f64.  Outputs: d_u2g [B,M], sched [B,M]
+ * (1 = served), rate_per_gt [B,M], reward [B] f64, done [B], observations obs_gt [B,M,4], obs_agent [B,2] and obs_flat
+ * [B, 2 + 4 M] = agent || gt row-major (gym's flatten of the key-sorted Dict space).  M <= 1024, else UAVGNN_EUNSUPPORTED.
+ * No host synchronisation, no allocation.  int_consts / f64_consts: HOST arrays, layout in csrc/subs_env.hip. */
+int uavgnn_subs_env_step(const int32_t* int_consts, const double* f64_consts, int B, const long long* actions,
+                         const double* avail_moves, double* pos_ubs, const float* pos_gts, int32_t* prior, float* avg_rate,
+                         int32_t* t, double* run_f64, float* d_u2g, int32_t* sched, float* rate_per_gt, double* reward,
+                         float* done, float* obs_gt, float* obs_agent, float* obs_flat, uavgnn_stream_t stream);
+
+/* Reset-time placements of the single-UBS environment, B environments per launch (reference: subs_cov.py:92-111
+ * _set_position, np.random.permutation at :84): the UBS at the centre, pos_ubs [B,2] f64; n_grps groups at angles
+ * (u + g / n_grps) 2 pi and radii uniform in [0.2, 0.3] range_pos; GTs at 0.25 r_cov N(0,1) per coordinate around their group,
+ * clipped to [0, range_pos], rows shuffled, pos_gts [B,M,2] f32; prior [B,M] a uniform permutation.  Counter-based
+ * Philox4x32-10 keyed as uavgnn_map_sample keys it: rng is a DEVICE array {seed, resets}, environment b's placement depends on
+ * (seed, resets, b) only.  Normals by Box-Muller, evaluated in double and rounded to float32 once.  M = n_grps gts_per_grp <=
+ * 1024, else UAVGNN_EUNSUPPORTED.  int_consts / f64_consts: HOST arrays; their layout, the draw slots and the rules are in
+ * csrc/subs_env.hip. */
+int uavgnn_subs_env_sample(const int32_t* int_consts, const double* f64_consts, int B, const long long* rng, double* pos_ubs,
+                           float* pos_gts, int32_t* prior, uavgnn_stream_t stream);
+
 /* The four construction passes above + the three prefix sums in ONE launch for small batches (B n <=
  * uavgnn_build_graph_small_max_agents() = 4096 agents; reference: env_wrappers.py:65-89,:122-154 for B environments): seen_off /
  * near_off / talk_off [B n + 1], graph_off [B + 1] and the compacted x_gt / x_ubs / talk_src / talk_eid (allocated by the

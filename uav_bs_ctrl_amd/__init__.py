@@ -7,6 +7,6 @@ the C-ABI of ``include/uavgnn.h``.  There is no CPU fallback.
 from .agents import REGISTRY, GnnAgent, RnnAgent  # noqa: F401
 from .tuned import enable_tuned_gemms  # noqa: F401  (opt-in, process-wide: see uav_bs_ctrl_amd/tuned)
 from .graph import (FlatObsBatch, HeteroBatch, batch, cat, from_obs_dicts, from_padded_obs, from_padded_obs_flat,  # noqa: F401
-                    heterograph, merge)
+                    from_single_ubs_obs, heterograph, merge)
 
 __version__ = "0.1.0"

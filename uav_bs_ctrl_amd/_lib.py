@@ -125,6 +125,8 @@ SIGNATURES = {
     "uavgnn_env_state_dim": (_c_int, [_c_int, _c_int, _c_int]),
     "uavgnn_env_step": (_c_int, [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double), _c_int] + [_c_fp] * 22 + [_c_st]),
     "uavgnn_map_sample": (_c_int, [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double), _c_int] + [_c_fp] * 6 + [_c_st]),
+    "uavgnn_subs_env_step": (_c_int, [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double), _c_int] + [_c_fp] * 16 + [_c_st]),
+    "uavgnn_subs_env_sample": (_c_int, [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double), _c_int] + [_c_fp] * 4 + [_c_st]),
     "uavgnn_adamw_polyak": (_c_int, [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, ctypes.c_longlong, ctypes.c_longlong, _c_fp, ctypes.c_double,
                                      ctypes.c_double, _c_f32, _c_f32, _c_f32, _c_f32, _c_st]),
     "uavgnn_gru_cell_supported": (_c_int, [_c_int, _c_int]),

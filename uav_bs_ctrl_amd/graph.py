@@ -553,7 +553,7 @@ _SCAN4_MAX_ROWS = 1 << 17   # one-launch scans (uavgnn_offsets_scan4) up to here
 
 def _uniform_graph_off(N, n, dev):
     """[0, n, 2n, ..., N] for a batch of equal-size graphs; read-only, shared between batches of the same shape."""
-    if th.cuda.is_current_stream_capturing():     # a tensor born inside a capture belongs to the graph's pool: never cached
+    if th.device(dev).type == "cuda" and th.cuda.is_current_stream_capturing():     # a tensor born inside a capture belongs to the graph's pool: never cached
         return th.arange(0, N + 1, n, dtype=th.int32, device=dev)
     key = (N, n, str(dev))
     t = _GRAPH_OFF_CACHE.get(key)
@@ -650,6 +650,22 @@ def from_padded_obs(gt: th.Tensor, ubs: th.Tensor, agent: th.Tensor, d_u2u: Opti
                 "uavgnn_talk_compact")
         kw.update(talk_off=talk_off, talk_src=talk_src, talk_eid=talk_eid)
     return HeteroBatch.from_arrays(device=dev, **kw)
+
+
+def from_single_ubs_obs(gt: th.Tensor, agent: th.Tensor) -> HeteroBatch:
+    """Observation graphs of B single-UBS environments (experiment 1): gt [B,M,4], agent [B,2] -> the `seen-by` batch the
+    reference's wrapper builds one graph at a time (algos/drqn/utils/env_wrappers.py:63-77: every GT of an environment is
+    connected to its one agent).  Equal, array for array, to ``batch`` of B ``heterograph``s.  No launch and no copy: ``x_gt`` is
+    the [B M, 4] view of ``gt``, the offsets are a cached arange(0, B M + 1, M), one agent per graph.  CPU tensors are accepted
+    (host-side checks); the agents themselves run on the GPU only."""
+    if gt.dim() != 3 or agent.dim() != 2 or gt.shape[0] != agent.shape[0]:
+        raise ValueError(f"from_single_ubs_obs: gt [B,M,F] and agent [B,Fa] expected, got {tuple(gt.shape)} / {tuple(agent.shape)}")
+    B, M, Fg = gt.shape
+    dev = gt.device
+    x_gt = gt.view(B * M, Fg) if gt.is_contiguous() else gt.reshape(B * M, Fg)
+    off = _uniform_graph_off(B * M, M, dev)
+    return HeteroBatch({"agent": B, "gt": B * M}, {SEEN_BY: _Relation(off)}, {"agent": {"feat": agent}, "gt": {"feat": x_gt}},
+                       _uniform_graph_off(B, 1, dev), {"max_graph_agents": 1, "max_deg:seen-by": M})
 
 
 # ---------------------------------------------------------------------------------------------------------------------

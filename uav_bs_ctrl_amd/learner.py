@@ -407,6 +407,54 @@ class MultiAgentQLearner:
         return dict(epoch=ck.get("epoch"), t=ck.get("t"))
 
 
+class QLearner(MultiAgentQLearner):
+    """Batched, device-resident counterpart of the single-agent DRQN learner of experiment 1 (algos/drqn/learner.py:15-150):
+    ``MultiAgentQLearner`` with ONE agent per environment, no mixer and ``max`` targets (:106, no double-Q).  ``act`` (one epsilon
+    draw per environment, :60-63, through uavgnn_eps_greedy), ``update`` / ``accumulate`` / ``apply`` with the fused optimizer tail,
+    LR annealing, the checkpoint keys and the data-parallel exchange are the parent's, unchanged; what differs is the agent that
+    is built (:48-52) and the replay scheme ``cache`` feeds (:67-73, ``replay.SingleUbsSequenceReplay``).
+
+    env_info: the wrapper's dict (``BatchedSingleUbsCoverageEnv.get_env_info``: obs_shape, n_actions, episode_limit).  args: the
+    reference's DRQN config (algos/drqn/config.py); ``dueling`` defaults to False when it is missing (the DRQN config has no
+    such switch), ``double_q`` and ``mixer`` are not read.  The caller's ``args`` object is left as it is."""
+
+    def __init__(self, env_info: dict, args, process_group=None):
+        import copy
+        args = copy.copy(args)
+        if not hasattr(args, "dueling"):
+            args.dueling = False
+        args.double_q, args.mixer = False, False
+        info = dict(env_info)
+        info["n_agents"] = 1
+        super().__init__(info, args, process_group)
+
+    def _build_agent(self):
+        """learner.py:48-52: an integer observation size -> 'rnn' (flattened observations), a dict of feature sizes -> the
+        DRQN's GNN agent (REGISTRY['gnn'] of algos/drqn/agents, registered here as 'drqn_gnn')."""
+        if isinstance(self.obs_shape, int):
+            return agent_REGISTRY["rnn"](self.obs_shape, self.n_actions, self.args)
+        return agent_REGISTRY["drqn_gnn"](self.obs_shape, self.n_actions, self.args)
+
+    def cache(self, buffer, obs: Dict, h, act, rew, next_obs: Dict, next_h, done, bad_mask, staged: bool = False) -> None:
+        """learner.py:67-73 for E parallel environments on the device: one transition per environment is pushed into ``buffer``
+        (a ``replay.SingleUbsSequenceReplay``) with the reference's two rules -
+          * the next hidden state is zeroed by the RAW done flag: ``next_h = (1 - done) * next_h``;
+          * the stored ``done`` is muted when the episode ended by its time limit: ``done = (1 - bad_mask) * done``.
+        obs / next_obs: the observation fields ``gt`` [E,M,4] and ``agent`` [E,2] (``env.observations()``); h / next_h [E, H]; act,
+        rew, done, bad_mask [E], [E,1] or scalars.  staged: the observation half (obs fields, h) was written with
+        ``buffer.stage_obs`` before the simulator overwrote its buffers - only act / rew / done / next_* are pushed."""
+        E, dev = buffer.n_envs, buffer.device
+        f32 = lambda x: th.as_tensor(x, dtype=th.float32, device=dev)   # noqa: E731
+        done_raw = f32(done).reshape(-1, 1).expand(E, 1)
+        bad = f32(0.0 if bad_mask is None else bad_mask).reshape(-1, 1).expand(E, 1)
+        tr = dict(act=th.as_tensor(act, device=dev).reshape(-1, 1).expand(E, 1).long(), rew=f32(rew).reshape(-1, 1).expand(E, 1),
+                  done=(1.0 - bad) * done_raw, next_h=(1.0 - done_raw) * f32(next_h).reshape(E, -1),
+                  next_gt=next_obs["gt"], next_agent=next_obs["agent"])
+        if not staged:
+            tr.update(h=f32(h).reshape(E, -1), gt=obs["gt"], agent=obs["agent"])
+        buffer.push(tr)
+
+
 def _mse(x: th.Tensor, y: th.Tensor) -> th.Tensor:
     """F.mse_loss(x, y) (learner.py:154: the mean of squared differences) as a TWO-STAGE sum: row sums of a [S, numel / S] view, then
     the sum of the S row sums.  torch's full reduction of a large tensor to one scalar runs as several thread blocks that meet at a

@@ -17,7 +17,7 @@ from typing import Dict, Optional
 
 import torch as th
 
-from .graph import HeteroBatch, from_obs_dicts, from_padded_obs, from_padded_obs_flat, batch as hb_batch
+from .graph import HeteroBatch, from_obs_dicts, from_padded_obs, from_padded_obs_flat, from_single_ubs_obs, batch as hb_batch
 
 SCHEME = ("gt", "ubs", "agent", "d_u2u", "h", "state", "act", "rew", "done")
 
@@ -120,6 +120,97 @@ class SequenceReplay:
                     gs.append(from_obs_dicts(o, m["d_u2u"][b, t].numpy(), self.r_comm))
                 obs.append(hb_batch(gs))
         out["obs"] = obs
+        return out
+
+    def sample(self, batch_size: int, generator: Optional[th.Generator] = None, enc: str = "gnn") -> Dict:
+        return self.gather(self.sample_indices(batch_size, generator), enc)
+
+
+SINGLE_UBS_SCHEME = ("gt", "agent", "h", "act", "rew", "done")
+
+
+class SingleUbsSequenceReplay:
+    """The DRQN's replay of experiment 1 (algos/drqn/buffer.py:5-36, scheme ('obs', 'h', 'act', 'rew', 'done')) in HBM: a ring of
+    fixed-length sequences of the single-UBS environment's observation FIELDS - gt [T+1, M, 4], agent [T+1, 2] - and the
+    recurrent state h [T+1, H], plus act / rew / done [T, 1] per sequence row.  Same sequence semantics as the reference: T
+    transitions, then the next observation / hidden state of the last one (buffer.py:23-25).  ``gather`` hands the learner either
+    the T+1 `seen-by` batches (``from_single_ubs_obs`` on views of the gathered fields: no graph is ever stored or copied) or the
+    T+1 flattened [B, 2+4M] tensors (agent || gt row-major)."""
+
+    def __init__(self, capacity: int, max_seq_len: int, n_gts: int, hidden_size: int, n_envs: int = 1, device="cuda"):
+        T, M = max_seq_len, n_gts
+        self.capacity, self.T, self.M, self.n_envs = capacity, T, M, n_envs
+        self.device = th.device(device)
+        f = dict(dtype=th.float32, device=self.device)
+
+        def ring(lead):  # committed sequences / sequences under construction (one per parallel env)
+            return dict(gt=th.zeros(lead, T + 1, M, 4, **f), agent=th.zeros(lead, T + 1, 2, **f),
+                        h=th.zeros(lead, T + 1, hidden_size, **f), act=th.zeros(lead, T, 1, dtype=th.int64, device=self.device),
+                        rew=th.zeros(lead, T, 1, **f), done=th.zeros(lead, T, 1, **f))
+        self.mem = ring(capacity)
+        self.cur = ring(n_envs)
+        self.ptr = 0            # time index inside the sequences under construction (buffer.py:15)
+        self.head = 0           # next ring slot
+        self.size = 0
+
+    def __len__(self) -> int:
+        return self.size
+
+    def push(self, tr: Dict[str, th.Tensor]) -> None:
+        """One transition of every parallel env.  tr: gt / agent / h [E, ...] (observation BEFORE the action; may be absent when
+        staged), act / rew / done [E,1] and next_gt / next_agent / next_h (buffer.py:17-29)."""
+        t = self.ptr
+        for k in ("gt", "agent", "h"):
+            if k in tr:
+                self.cur[k][:, t] = tr[k]
+        for k in ("act", "rew", "done"):
+            self.cur[k][:, t] = tr[k]
+        self.ptr += 1
+        if self.ptr == self.T:
+            for k in ("gt", "agent", "h"):
+                if "next_" + k in tr:
+                    self.cur[k][:, self.T] = tr["next_" + k]
+            E = self.n_envs
+            slots = (self.head + th.arange(E, device=self.device)) % self.capacity
+            for k in SINGLE_UBS_SCHEME:
+                self.mem[k][slots] = self.cur[k]
+            self.head = (self.head + E) % self.capacity
+            self.size = min(self.size + E, self.capacity)
+            self.ptr = 0
+
+    def stage_obs(self, tr: Dict[str, th.Tensor]) -> None:
+        """The observation half of the current transition (gt / agent / h BEFORE the action), written at the current step
+        WITHOUT advancing: the simulator overwrites its observation buffers in place, so it can be stepped before ``push``
+        receives act / rew / done / next_* - no clone of the observation in between."""
+        t = self.ptr
+        for k in ("gt", "agent", "h"):
+            if k in tr:
+                self.cur[k][:, t] = tr[k]
+
+    def sample_indices(self, batch_size: int, generator: Optional[th.Generator] = None) -> th.Tensor:
+        """Without replacement, like ``random.sample`` (buffer.py:31-33)."""
+        assert self.size >= batch_size, "Insufficient samples for update."
+        return th.randperm(self.size, generator=generator, device=self.device)[:batch_size]
+
+    def gather(self, idx: th.Tensor, enc: str = "gnn") -> Dict:
+        """Batch dict in the layout ``MultiAgentQLearner.loss`` consumes (one agent per environment): obs = T+1 `seen-by`
+        HeteroBatch of B environments (enc='gnn') or T+1 [B, 2+4M] tensors (enc='rnn'), h0 / h1 [B, H], acts / rews / dones
+        [T, B, 1].  The observation fields are gathered TIME-MAJOR in the one copy of the gather, so every step is a view."""
+        if enc not in ("gnn", "rnn"):
+            raise ValueError(f"enc must be 'gnn' or 'rnn', got {enc!r}")
+        B = idx.numel()
+        gt = self.mem["gt"].transpose(0, 1).index_select(1, idx)              # [T+1, B, M, 4]
+        agent = self.mem["agent"].transpose(0, 1).index_select(1, idx)        # [T+1, B, 2]
+        h = self.mem["h"][:, :2].index_select(0, idx)
+        out = dict(h0=h[:, 0].contiguous(), h1=h[:, 1].contiguous(),
+                   acts=self.mem["act"].index_select(0, idx).transpose(0, 1).contiguous(),
+                   rews=self.mem["rew"].index_select(0, idx).transpose(0, 1).contiguous(),
+                   dones=self.mem["done"].index_select(0, idx).transpose(0, 1).contiguous())
+        if enc == "gnn":
+            out["obs"] = [from_single_ubs_obs(gt[t], agent[t]) for t in range(self.T + 1)]
+        else:
+            flat = th.cat((agent, gt.reshape(self.T + 1, B, -1)), 2)          # [T+1, B, 2+4M]
+            out["obs"] = [flat[t] for t in range(self.T + 1)]
         return out
 
     def sample(self, batch_size: int, generator: Optional[th.Generator] = None, enc: str = "gnn") -> Dict:

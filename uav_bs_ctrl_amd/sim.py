@@ -20,6 +20,9 @@ The reference's own maps and placements: ``MAPS`` holds its eight registered map
 
 draws what ``Map.set_positions`` + ``np.random.permutation`` draw - UBSs on distinct lattice points, GTs in a shuffled hotspot
 - from a counter-based generator keyed by a device ``{seed, resets}`` pair, so the reset is reproducible and graph-capturable.
+
+Experiment 1's single-UBS environment (envs/subs_cov/subs_cov.py) has its own pair at the end of this module: ``SingleUbsParams`` and
+``BatchedSingleUbsCoverageEnv`` (csrc/subs_env.hip).
 """
 from __future__ import annotations
 
@@ -32,7 +35,7 @@ import numpy as np
 import torch as th
 
 from . import _lib as L
-from .graph import from_padded_obs
+from .graph import from_padded_obs, from_single_ubs_obs
 
 
 @dataclasses.dataclass
@@ -309,3 +312,172 @@ class BatchedUbsCoverageEnv:
                     TotalThroughput=self.run_f32[:, 0], ProbCollision=self.n_colls / self.t.clamp(min=1),
                     BadMask=o["done"])                       # the only termination is the episode limit (:343-345)
         return self.observations(), o["reward"], o["done"], info
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Experiment 1: the single-UBS environment (envs/subs_cov/subs_cov.py), csrc/subs_env.hip
+@dataclasses.dataclass
+class SingleUbsParams:
+    """Arguments of ``SingleUbsCoverageEnv.__init__`` (subs_cov.py:22-23) + its class constants (:13-20)."""
+    range_pos: float = 1000.0
+    episode_limit: int = 200
+    n_grps: int = 2
+    gts_per_grp: int = 1
+    r_cov: float = 100.0
+    n_rbs: int = 10
+    vels: Union[float, tuple] = 10.0
+    n_dirs: int = 4
+    unit: float = 100.0
+    h_ubs: float = 100.0
+    p_tx: float = 1e-3 * 10 ** (10 / 10)
+    n0: float = 1e-3 * 10 ** (-170 / 10)
+    bw: float = 180e3
+    fc: float = 2.4e9
+    dt: float = 10.0
+    scene: str = "urban"
+
+    @property
+    def n_gts(self) -> int:
+        return self.n_grps * self.gts_per_grp
+
+    @property
+    def reward_scale_rate(self) -> float:
+        return float(self.n_grps)                                                               # subs_cov.py:67
+
+    def chan(self):
+        return MapParams.CHAN[self.scene]
+
+    @property
+    def max_rate(self) -> float:
+        """subs_cov.py:35-38: the rate of the link straight below the UBS, in float64."""
+        a, b, eta_los, eta_nlos = self.chan()
+        p_los = 1 / (1 + a * math.exp(-b * (math.atan(self.h_ubs / (0.0 + 1e-5)) - a)))
+        d = math.sqrt(0.0 ** 2 + self.h_ubs ** 2)
+        fspl = (4 * math.pi * self.fc * d / 3e8) ** 2
+        pl = p_los * fspl * 10 ** (eta_los / 20) + (1 - p_los) * fspl * 10 ** (eta_nlos / 20)
+        snr_max = self.p_tx * (1 / pl) / (self.n0 * self.bw)
+        return self.bw * math.log2(1 + snr_max) * 1e-6
+
+    def avail_moves(self) -> np.ndarray:
+        """subs_cov.py:56-59: hover + |vels| x n_dirs displacement vectors."""
+        amounts = self.dt * np.array(self.vels, dtype=np.float64).reshape(-1, 1)
+        ang = 2 * np.pi * np.arange(self.n_dirs) / self.n_dirs
+        dirs = np.stack([np.cos(ang), np.sin(ang)]).T
+        return np.ascontiguousarray(np.concatenate((np.zeros((1, 2)), np.kron(amounts, dirs))))
+
+
+class BatchedSingleUbsCoverageEnv:
+    """B independent ``SingleUbsCoverageEnv``s on the device, one launch per step (csrc/subs_env.hip); the interface of
+    ``BatchedUbsCoverageEnv``.
+
+        env = BatchedSingleUbsCoverageEnv(SingleUbsParams(n_grps=2, gts_per_grp=5), B=4096, seed=0)
+        obs = env.reset()                                  # placements drawn on the device: one sampler launch + one step launch
+        obs, reward, done, info = env.step(actions)        # actions [B] int64 on the device
+        g = env.graph()                                    # the `seen-by` HeteroBatch of the current observations (no launch)
+    """
+
+    def __init__(self, p: SingleUbsParams, B: int, device="cuda", seed: Optional[int] = None):
+        self.p, self.B, self.device = p, B, th.device(device)
+        M = p.n_gts
+        self.n_gts = M
+        moves = p.avail_moves()
+        self.n_actions = moves.shape[0]
+        self.episode_limit = p.episode_limit
+        self.max_rate = p.max_rate
+        a, b, eta_los, eta_nlos = p.chan()
+        self._ic = (ctypes.c_int32 * 5)(M, p.n_rbs, self.n_actions, p.episode_limit, p.n_grps)
+        self._fc = (ctypes.c_double * 14)(p.range_pos, p.r_cov, p.dt, p.h_ubs, p.p_tx, p.n0, p.bw, p.fc, a, b, eta_los, eta_nlos,
+                                          p.reward_scale_rate, self.max_rate)
+        self._sample_ic = (ctypes.c_int32 * 2)(p.n_grps, p.gts_per_grp)
+        self._sample_fc = (ctypes.c_double * 2)(p.range_pos, p.r_cov)
+        dev = self.device
+        f32, f64, i32 = (dict(dtype=d, device=dev) for d in (th.float32, th.float64, th.int32))
+        self.moves = th.as_tensor(moves, **f64).contiguous()
+        self.pos_ubs, self.pos_gts = th.zeros(B, 2, **f64), th.zeros(B, M, 2, **f32)
+        self.prior, self.avg_rate, self.t = th.zeros(B, M, **i32), th.zeros(B, M, **f32), th.zeros(B, **i32)
+        self.run_f64 = th.zeros(B, 4, **f64)
+        self.out = dict(d_u2g=th.zeros(B, M, **f32), sched=th.zeros(B, M, **i32), rate_per_gt=th.zeros(B, M, **f32),
+                        reward=th.zeros(B, **f64), done=th.zeros(B, **f32), obs_gt=th.zeros(B, M, 4, **f32),
+                        obs_agent=th.zeros(B, 2, **f32), obs_flat=th.zeros(B, 2 + 4 * M, **f32))
+        self.ep_ret = th.zeros(B, **f64)
+        if seed is None:                                     # from torch's default generator: torch.manual_seed reproduces a run
+            seed = int(th.randint(0, 2 ** 62, (1,)).item())
+        self.rng = th.tensor([int(seed), 0], dtype=th.int64, device=dev)     # device {seed, resets} of the placement sampler
+
+    # ---- the two kernels ---------------------------------------------------------------------------------------------
+    def _launch(self, actions: Optional[th.Tensor]):
+        L.require_gpu(self.pos_ubs, actions)
+        o = self.out
+        if actions is not None:
+            actions = actions.to(th.int64).contiguous()
+            if actions.numel() != self.B:
+                raise ValueError(f"actions must hold one action per environment ({self.B}), got {tuple(actions.shape)}")
+        L.check(L.lib().uavgnn_subs_env_step(self._ic, self._fc, self.B, L.ptr(actions), self.moves.data_ptr(),
+                                             self.pos_ubs.data_ptr(), self.pos_gts.data_ptr(), self.prior.data_ptr(),
+                                             self.avg_rate.data_ptr(), self.t.data_ptr(), self.run_f64.data_ptr(),
+                                             o["d_u2g"].data_ptr(), o["sched"].data_ptr(), o["rate_per_gt"].data_ptr(),
+                                             o["reward"].data_ptr(), o["done"].data_ptr(), o["obs_gt"].data_ptr(),
+                                             o["obs_agent"].data_ptr(), o["obs_flat"].data_ptr(), L.stream()),
+                "uavgnn_subs_env_step")
+
+    def _sample_into(self, pos_ubs: th.Tensor, pos_gts: th.Tensor, prior: th.Tensor):
+        """One uavgnn_subs_env_sample launch at the current {seed, resets}; then resets += 1 on the device (capturable)."""
+        L.require_gpu(pos_ubs, pos_gts, prior, self.rng)
+        L.check(L.lib().uavgnn_subs_env_sample(self._sample_ic, self._sample_fc, self.B, self.rng.data_ptr(), pos_ubs.data_ptr(),
+                                               pos_gts.data_ptr(), prior.data_ptr(), L.stream()), "uavgnn_subs_env_sample")
+        self.rng[1:].add_(1)
+
+    def sample_positions(self):
+        """(pos_ubs [B,2] f64, pos_gts [B,M,2] f32, prior [B,M] i32) as ``_set_position`` + the reset's ``np.random.permutation``
+        draw them (subs_cov.py:92-111, :84), in fresh tensors; advances the reset counter."""
+        B, M, dev = self.B, self.n_gts, self.device
+        out = (th.empty(B, 2, dtype=th.float64, device=dev), th.empty(B, M, 2, dtype=th.float32, device=dev),
+               th.empty(B, M, dtype=th.int32, device=dev))
+        self._sample_into(*out)
+        return out
+
+    def observations(self) -> Dict[str, th.Tensor]:
+        """The observation of the current state in both forms of the reference's wrapper: the Dict fields ``gt`` [B,M,4] and
+        ``agent`` [B,2] (subs_cov.py:159-171) and ``flat`` [B, 2+4M], their gym ``flatten`` (env_wrappers.py:51-53)."""
+        o = self.out
+        return dict(gt=o["obs_gt"], agent=o["obs_agent"], flat=o["obs_flat"])
+
+    def graph(self):
+        """`seen-by` HeteroBatch of the current observations (drqn/utils/env_wrappers.py:63-77 for B environments): views, no launch."""
+        return from_single_ubs_obs(self.out["obs_gt"], self.out["obs_agent"])
+
+    def reset(self, pos_ubs=None, pos_gts=None, prior=None):
+        """subs_cov.py:75-90.  An explicit state - pos_ubs [B,2], pos_gts [B,M,2], prior [B,M] (a permutation of the GTs per
+        environment) - or, when all three are None, the placements of the device sampler.  Then the running state is zeroed and the
+        reset-time transmission runs (:85).  No host synchronisation, fixed addresses."""
+        given = [x is not None for x in (pos_ubs, pos_gts, prior)]
+        if not any(given):
+            self._sample_into(self.pos_ubs, self.pos_gts, self.prior)
+        elif all(given):
+            self.pos_ubs.copy_(th.as_tensor(pos_ubs, dtype=th.float64).reshape(self.B, 2))
+            self.pos_gts.copy_(th.as_tensor(pos_gts).to(th.float32))
+            self.prior.copy_(th.as_tensor(prior).to(th.int32))
+        else:
+            raise ValueError("reset: give pos_ubs, pos_gts and prior together, or none of them (the sampler draws all three)")
+        for t_ in (self.avg_rate, self.t, self.run_f64, self.ep_ret):
+            t_.zero_()
+        self._launch(None)
+        return self.observations()
+
+    def step(self, actions: th.Tensor):
+        """subs_cov.py:113-133.  actions [B] int64 on the device.  Returns (observations, reward [B] f64, done [B] f32, info
+        dict of device tensors with the reference's keys) - nothing is synchronised with the host."""
+        self._launch(actions.reshape(self.B))
+        o = self.out
+        self.ep_ret += o["reward"]
+        info = dict(EpRet=self.ep_ret, EpLen=self.t, AvgGlobalUtility=self.run_f64[:, 1], FairIdx=self.run_f64[:, 2],
+                    TotalThroughput=self.run_f64[:, 0], BadMask=o["done"])     # the only termination is the episode limit (:126)
+        return self.observations(), o["reward"], o["done"], info
+
+    def get_env_info(self, agent: str = "gnn") -> dict:
+        """The wrapper's ``get_env_info`` (drqn/utils/env_wrappers.py:21-25): agent 'gnn' -> the graph observation's feature
+        sizes, 'rnn' -> the flattened width."""
+        if agent not in ("gnn", "rnn"):
+            raise ValueError(f"agent must be 'gnn' or 'rnn', got {agent!r}")
+        obs_shape = 2 + 4 * self.n_gts if agent == "rnn" else dict(agent=2, gt=4)
+        return dict(obs_shape=obs_shape, n_actions=self.n_actions, episode_limit=self.episode_limit)
