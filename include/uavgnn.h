@@ -530,6 +530,26 @@ int uavgnn_row_absmax(const float* a1, int ld1, int K1, const float* a2, int ld2
 int uavgnn_head_supported(int H, int A);
 int uavgnn_head_fwd(const float* h, int ld_h, int N, int H, const float* W, int ld_w, const float* b, int A, float* q, int ld_q,
                     uavgnn_stream_t stream);
+/* The recurrent half of nn.GRUCell for FEW rows (csrc/gru_rec.hip; reference: the GRU cells of the agents without a communication
+ * block - algos/drqn/agents/gnn_agents.py:25-29, algos/madrqn/agents/rnn_agents.py:22-26, gnn_agents.py:29 - at 32 sequences x 1 or 8
+ * agents): the input projection gi = x W_ih^T + b_ih does not depend on h, so the caller forms it for all steps of a sequence in one
+ * GEMM and only this half walks the sequence.  Parallel over (16-row tile) x (16 hidden columns); exact fp32 products, fp32
+ * accumulation on v_mfma_f32_16x16x4_f32 in a fixed order; bit-reproducible.  uavgnn_gru_rec_supported: H % 16 == 0, 16 <= H <= 256.
+ *   fwd  gi [N, 3H] (row stride ld_gi; b_ih included; gate order r | z | n), h [N, H] (ld_h), W_hh [3H, H], b_hh [3H] ->
+ *        h_out [N, H] (ld_ho) = (1 - z) n + z h; pre_save (may be NULL): [N, 4H] = r_pre | z_pre | gi_n | gh_n, the set
+ *        uavgnn_gru_cell_fwd saves.
+ *   bwd  pre [N, 4H], h [N, H] (ld_h), d_hout / d_carry (each may be NULL; contiguous [N, H]; their sum is the gradient of h') ->
+ *        d_gi, d_gh [N, 3H] as uavgnn_gru_gates_bwd_fused writes them and dh_prev [N, H] = dh z + d_gh W_hh.
+ * Rows >= N are never written.  Leading dimensions are multiples of 4 floats and every base is 16-byte aligned
+ * (UAVGNN_EUNSUPPORTED otherwise).  Workgroups read whole rows of h (d_hout / d_carry) while others write column blocks of h_out
+ * (dh_prev): an h_out whose ADDRESS RANGE [base, base + 4 ((N - 1) ld + H)) intersects h's, or a dh_prev whose range intersects
+ * d_hout's / d_carry's, is UAVGNN_EINVAL before any launch - the ranges are compared, not the elements, so two disjoint column views of
+ * one wider buffer (h = buf[:, :H], h_out = buf[:, H:]) are refused as well. */
+int uavgnn_gru_rec_supported(int H);
+int uavgnn_gru_rec_fwd(const float* gi, int ld_gi, const float* h, int ld_h, int N, int H, const float* W_hh, const float* b_hh,
+                       float* h_out, int ld_ho, float* pre_save, uavgnn_stream_t stream);
+int uavgnn_gru_rec_bwd(const float* pre, const float* h, int ld_h, const float* d_hout, const float* d_carry, int N, int H,
+                       const float* W_hh, float* d_gi, float* d_gh, float* dh_prev, uavgnn_stream_t stream);
 /* Dense layers on the bf16 matrix cores (csrc/gemm_x3.hip; reference: the nn.Linear layers of
  * algos/madrqn/agents/gnn_agents.py - f_aggr :101-102, :106, TarMAC projections :227-236 - and the input-gradient GEMMs of
  * loss.backward(), learner.py:157): Y[M, N] = X[M, K] B[N, K]^T (+ bias[N]) (+ Y) (then ReLU), fp32 in / out, each fp32 product

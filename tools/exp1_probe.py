@@ -6,6 +6,14 @@ csrc/subs_env.hip alone at B = 1 / 32 / 4096; and - where the reference is impor
 oracle/) - the reference environment's own ``step`` rate on the host, one instance, in the same run.
 
     python tools/exp1_probe.py [--envs 32 4096] [--steps 200] [--reference /path/to/uav_bs_ctrl] [--host-only]
+    python tools/exp1_probe.py --ab [--agents gnn rnn] [--repeats 3]
+
+--ab: the rows that decide the default of ``ops.GRU_SEQ`` at the reference's operating point (32 environments / 32 sequences x T = 10 x
+H = 256 x 1 x 20), per agent: the update alone, the 10-step rollout and the cycle, each on three arms - `per-step` (ops.GRU_SEQ off and
+``gather(time_batched=False)``: 2T + 1 separate forwards, the launch sequence of the commit before the sequence route - on THIS tree, whose
+``DrqnGnnAgent.forward`` is ``step(encode())``; the baseline proper is that commit's own checkout running its own probe, recorded next to these rows
+in profiles/exp1_probe.txt), `sequence` (the defaults, eager) and `graphed`
+(``graphs.GraphedSingleUbsAct`` on the simulator's buffers / ``GraphedSingleUbsUpdate`` replayed) - every arm repeated --repeats times.
 
 Measurements, not thresholds: host clock around work that ends in a device synchronise, after a warm-up of every shape."""
 import argparse
@@ -89,6 +97,73 @@ def device_rates(B, steps):
                 cycle_ms=1e3 * t_cyc, cycle_env_steps_per_s=B * T_SEQ / t_cyc, update_batch=UPDATE_BATCH, seq_len=T_SEQ)
 
 
+def ab_rows(agent, repeats, iters=20):
+    """[{phase, arm, ms: [one mean per repeat]}] for `agent` at the reference's operating point."""
+    import torch as th
+
+    from uav_bs_ctrl_amd import ops
+    from uav_bs_ctrl_amd.graphs import GraphedSingleUbsAct, GraphedSingleUbsUpdate
+    from uav_bs_ctrl_amd.learner import QLearner
+    from uav_bs_ctrl_amd.replay import SingleUbsSequenceReplay
+    from uav_bs_ctrl_amd.sim import BatchedSingleUbsCoverageEnv, SingleUbsParams
+    B = UPDATE_BATCH
+    p = SingleUbsParams(episode_limit=200, **C1)
+    env = BatchedSingleUbsCoverageEnv(p, B, seed=0)
+    args = types.SimpleNamespace(device="cuda", agent=agent, hidden_size=256, n_heads=4, n_layers=2, max_seq_len=T_SEQ, gamma=0.99,
+                                 polyak=0.999, batch_size=UPDATE_BATCH, lr=5e-4, anneal_lr=False, seed=0)
+    learner = QLearner(env.get_env_info(agent), args)
+    buf = SingleUbsSequenceReplay(4 * B, T_SEQ, p.n_gts, 256, n_envs=B, device="cuda")
+    state = dict(obs=env.reset(), h=learner.init_hidden(B), t=0)
+    ga = GraphedSingleUbsAct(learner, B, p.n_gts, agent, obs=(env.out["obs_gt"], env.out["obs_agent"]))
+    gu = GraphedSingleUbsUpdate(learner, B, T_SEQ, p.n_gts, agent)
+    obs_in = (lambda: env.graph()) if agent == "gnn" else (lambda: env.observations()["flat"])
+
+    def rollout(graphed):
+        for _ in range(T_SEQ):
+            obs, h = state["obs"], state["h"]
+            if graphed:
+                a, h2 = ga(None, None, h, 0.1)
+                h2 = h2.clone()          # the graph's output buffer is overwritten by the next replay; the replay stores h AND h'
+            else:
+                a, h2 = learner.act(obs_in(), h, 0.1)
+            buf.stage_obs(dict(gt=obs["gt"], agent=obs["agent"], h=h))
+            obs, rew, done, info = env.step(a)
+            learner.cache(buf, None, None, a, rew, obs, h2, done, info["BadMask"], staged=True)
+            state["t"] += 1
+            if state["t"] % p.episode_limit == 0:
+                obs, h2 = env.reset(), learner.init_hidden(B)
+            state["obs"], state["h"] = obs, h2
+
+    def update(arm):
+        idx = buf.sample_indices(UPDATE_BATCH)
+        if arm == "graphed":
+            return gu({k: v.index_select(0, idx) for k, v in buf.mem.items()})
+        return learner.update(buf.gather(idx, agent, time_batched=arm == "sequence"))
+
+    def timed(fn):
+        th.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            fn()
+        th.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0) / iters
+    for _ in range(4):
+        rollout(False)
+    rows = []
+    phases = (("update", lambda arm: update(arm)), ("rollout of 10 steps", lambda arm: rollout(arm == "graphed")),
+              ("cycle", lambda arm: (rollout(arm == "graphed"), update(arm))))
+    for phase, fn in phases:
+        for arm in ("per-step", "sequence", "graphed"):
+            if phase.startswith("rollout") and arm == "sequence":
+                continue                  # `act` has one eager path: the rollout gains from the capture only
+            ops.GRU_SEQ = arm != "per-step"
+            fn(arm), fn(arm)
+            rows.append(dict(what=f"exp1 {agent}, 32 x T=10 x H=256, 1 x 20", phase=phase, arm=arm, iters=iters,
+                             ms=[round(timed(lambda: fn(arm)), 4) for _ in range(repeats)]))
+    ops.GRU_SEQ = True
+    return rows
+
+
 def kernel_times(reps=2000):
     """Launch-to-launch time of each kernel alone (back-to-back launches, one synchronise at the end)."""
     import torch as th
@@ -120,7 +195,15 @@ def main():
     ap.add_argument("--steps", type=int, default=200, help="environment steps per timed window and configuration")
     ap.add_argument("--reference", default=None, help="checkout of the reference project (its host `step` rate is measured in this run)")
     ap.add_argument("--host-only", action="store_true", help="only the reference environment's host rate (no GPU needed)")
+    ap.add_argument("--ab", action="store_true", help="per-step / sequence / graphed arms of update, rollout and cycle at 32 x T=10 x H=256")
+    ap.add_argument("--agents", nargs="+", default=["gnn", "rnn"])
+    ap.add_argument("--repeats", type=int, default=3)
     a = ap.parse_args()
+    if a.ab:
+        for agent in a.agents:
+            for r in ab_rows(agent, a.repeats):
+                print(json.dumps(r), flush=True)
+        return
     rows = []
     if a.reference and os.path.isdir(os.path.join(a.reference, "envs", "subs_cov")):
         rows.append(reference_step_rate(a.reference, max(a.steps, 2000)))

@@ -164,6 +164,9 @@ SIGNATURES = {
     "uavgnn_gemm_x3_supported": (_c_int, [_c_int, _c_int, _c_int]),
     "uavgnn_head_supported": (_c_int, [_c_int, _c_int]),
     "uavgnn_head_fwd": (_c_int, [_c_fp, _c_int, _c_int, _c_int, _c_fp, _c_int, _c_fp, _c_int, _c_fp, _c_int, _c_st]),
+    "uavgnn_gru_rec_supported": (_c_int, [_c_int]),
+    "uavgnn_gru_rec_fwd": (_c_int, [_c_fp, _c_int, _c_fp, _c_int, _c_int, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_st]),
+    "uavgnn_gru_rec_bwd": (_c_int, [_c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_int, _c_int, _c_fp, _c_fp, _c_fp, _c_fp, _c_st]),
     "uavgnn_split_bf16x3": (_c_int, [_c_fp, _c_int, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_st]),
     "uavgnn_gemm_nt_x3": (_c_int, [_c_fp, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_int, _c_fp, _c_fp, _c_int, _c_int, _c_st]),
     "uavgnn_gemm_nt_x3_cat": (_c_int, [_c_fp, _c_int, _c_int, _c_fp, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_int, _c_fp, _c_fp, _c_int,

@@ -129,6 +129,14 @@ def _head(f_out, h):
     return ops.linear(h, f_out.weight, f_out.bias)
 
 
+def _unroll(cell: nn.GRUCell, f_out, x_all, h0, T1):
+    """Recurrence + Q head of an agent without a communication block over T1 time-major steps: q_all [T1, N, n_actions].  Nothing in
+    a step depends on another agent, so the input projection and the head run ONCE over all steps (ops.gru_unroll)."""
+    h_all = ops.gru_unroll(x_all, h0, cell, T1)
+    N, H = h_all.shape[1], h_all.shape[2]
+    return _head(f_out, h_all.reshape(T1 * N, H)).view(T1, N, -1)
+
+
 def _parent(g) -> HeteroBatch:
     return g.parent if isinstance(g, RelationView) else g
 
@@ -378,6 +386,13 @@ class GnnAgent(nn.Module):
             return ops.tarmac_step(x, h, g, comm, self.f_out, stacked=(Wp, bp), dx_out=dx_out)
         return ops.tarmac_step(x, h, g, comm, self.f_out, dx_out=dx_out)
 
+    def unroll(self, x_all, h0, T1):
+        """q_all [T1, N, n_actions] from the pre-encoded observations of T1 time-major steps (c=None only: with a communication
+        block a step depends on the other agents' hidden states of the same step)."""
+        if self._comm_protocol is not None:
+            raise ops.L.UavGnnError("GnnAgent.unroll: only the agent without a communication block (c=None) unrolls over time")
+        return _unroll(self.rnn, self.f_out, x_all, h0, T1)
+
     def forward(self, g: HeteroBatch, h):
         return self.step(g, self.encode(g), h)
 
@@ -396,10 +411,24 @@ class DrqnGnnAgent(nn.Module):
     def init_hidden(self):
         return th.zeros(1, self._hidden_size)
 
-    def forward(self, g: HeteroBatch, h):
+    def encode(self, g: HeteroBatch):
+        """Observation encoder only: x [N, H] (independent of h: the learner encodes all T+1 steps in one K1 launch)."""
         et = "seen-by" if g.has_relation("seen-by") else "seen"
         x_src, off = g.relation_segments(et)
-        x = self.enc(x_src, off, g.agent_feat(), g.relation_order(et)).flatten(start_dim=1)
+        return self.enc(x_src, off, g.agent_feat(), g.relation_order(et)).flatten(start_dim=1)
+
+    def step(self, g: HeteroBatch, x, h, dx_out=None):
+        """GRU cell + Q head on pre-encoded observations x (the meaning of GnnAgent.step; dx_out is not used: no fused step here)."""
+        n = x.shape[0]
+        if h.shape[0] != n:
+            h = h.expand(n, -1)
         h = _gru(self.rnn, (x,), h.contiguous())
         return ops.linear(h, self.f_out.weight, self.f_out.bias), h
+
+    def unroll(self, x_all, h0, T1):
+        """q_all [T1, N, n_actions] from the pre-encoded observations of T1 time-major steps."""
+        return _unroll(self.rnn, self.f_out, x_all, h0, T1)
+
+    def forward(self, g: HeteroBatch, h):
+        return self.step(g, self.encode(g), h)
 

@@ -16,7 +16,7 @@ import torch as th
 import torch.nn as nn
 
 from ..graph import FlatObsBatch, HeteroBatch
-from .gnn_agents import _gru, _head, mlp_encode
+from .gnn_agents import _gru, _head, _unroll, mlp_encode
 from .heads import DuelingLayer
 
 
@@ -53,6 +53,10 @@ class RnnAgent(nn.Module):
             h = h.expand(n, -1)
         h = _gru(self.rnn, (x,), h.contiguous())
         return _head(self.f_out, h), h
+
+    def unroll(self, x_all, h0, T1):
+        """q_all [T1, N, n_actions] from the pre-encoded observations of T1 time-major steps (GnnAgent.unroll)."""
+        return _unroll(self.rnn, self.f_out, x_all, h0, T1)
 
     def forward(self, obs, h):
         return self.step(obs, self.encode(obs), h)

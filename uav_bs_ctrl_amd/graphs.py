@@ -15,7 +15,7 @@ from typing import Dict, Optional
 import torch as th
 
 from . import _lib as L
-from .graph import from_padded_obs, from_padded_obs_flat
+from .graph import from_padded_obs, from_padded_obs_flat, from_single_ubs_obs
 
 
 def _builder(enc: str):
@@ -74,24 +74,14 @@ class _PaddedObs:
             self.d_u2u.copy_(d_u2u, non_blocking=True)
 
 
-class GraphedAct:
-    """``learner.act`` on B environments as one graph replay: device-side graph construction from padded observations,
-    no-grad policy forward, epsilon-greedy selection (one draw per team, learner.py:75-78).
+class _GraphedActBase:
+    """What the captured rollout steps share: the warm-up and capture of ``_body`` with the learner's generator registered, the
+    epsilon-greedy selection from device-resident epsilon, and the replay.  A subclass sets ``learner``, ``B`` (teams), ``h_in`` and
+    its observation buffers, defines ``_obs()`` (the observation batch built from those buffers) and calls ``_capture_act``."""
 
-        ga = GraphedAct(learner, B, n, M, r_comm)
-        acts, h = ga(gt, ubs, agent, d_u2u, h, eps)        # acts [B*n] int64, h' [B*n, H]; both are the graph's buffers
-
-    enc='mlp': flattened-observation batches (exp2) instead of observation graphs.
-    """
-
-    def __init__(self, learner, B: int, n: int, M: int, r_comm: float = float("inf"), warmup: int = 2, enc: str = "gnn"):
-        self.learner, self.B, self.n, self.M, self.r_comm = learner, B, n, M, r_comm
-        self._build = _builder(enc)
-        dev = learner.device
-        with_comm = learner.args.c is not None
-        self.obs = _PaddedObs((B,), n, M, dev, with_comm)
-        self.h_in = th.zeros(B * n, learner.args.hidden_size, dtype=th.float32, device=dev)
-        self.eps = th.zeros(1, dtype=th.float32, device=dev)
+    def _capture_act(self, warmup: int):
+        learner = self.learner
+        self.eps = th.zeros(1, dtype=th.float32, device=learner.device)
         self._eps_host = None
         self.graph = th.cuda.CUDAGraph()
         if hasattr(self.graph, "register_generator_state"):
@@ -108,8 +98,7 @@ class GraphedAct:
     @th.no_grad()
     def _body(self):
         lr = self.learner
-        g = self._build(self.obs.gt, self.obs.ubs, self.obs.agent, self.obs.d_u2u, self.r_comm, static=True)
-        logits, h = lr.policy_net(g, self.h_in)
+        logits, h = lr.policy_net(self._obs(), self.h_in)
         N = logits.shape[0]
         u = th.rand(self.B + N, device=lr.device, generator=lr._gen)
         acts = th.empty(N, dtype=th.int64, device=lr.device)
@@ -119,11 +108,7 @@ class GraphedAct:
                                               acts.data_ptr(), L.stream()), "uavgnn_eps_greedy_dev")
         return acts, h
 
-    def __call__(self, gt, ubs, agent, d_u2u, h, eps_thres: float):
-        """Copies the observation into the graph's buffers and replays.  A producer that writes ``self.obs.gt / .ubs /
-        .agent / .d_u2u`` and ``self.h_in`` in place (e.g. a device-side simulator) passes gt=None and skips the copies."""
-        if gt is not None:
-            self.obs.load(gt, ubs, agent, d_u2u)
+    def _replay(self, h, eps_thres: float):
         if h is not None and h.data_ptr() != self.h_in.data_ptr():
             self.h_in.copy_(h if h.shape[0] == self.h_in.shape[0] else h.expand_as(self.h_in), non_blocking=True)
         if eps_thres != self._eps_host:
@@ -133,35 +118,91 @@ class GraphedAct:
         return self.acts, self.h_out
 
 
-class GraphedUpdate:
-    """``learner.update`` on B stored sequences of T transitions as one graph replay: graphs of all T+1 steps rebuilt on
-    the device from the padded observations of the sampled batch (``SequenceReplay.mem`` layout), time-batched encoder,
-    2T+1 forwards, BPTT backward, clip + AdamW + polyak.
+class GraphedAct(_GraphedActBase):
+    """``learner.act`` on B environments as one graph replay: device-side graph construction from padded observations,
+    no-grad policy forward, epsilon-greedy selection (one draw per team, learner.py:75-78).
 
-        gu = GraphedUpdate(learner, B, T, n, M, r_comm)
-        out = gu(batch)      # batch: gt [B,T+1,n,M,5], ubs, agent, d_u2u, h [B,T+1,n,H], act [B,T,n], rew [B,T,rd], done [B,T,1]
+        ga = GraphedAct(learner, B, n, M, r_comm)
+        acts, h = ga(gt, ubs, agent, d_u2u, h, eps)        # acts [B*n] int64, h' [B*n, H]; both are the graph's buffers
 
-    Data-parallel runs (``learner.needs_collective()``): the gradient all-reduce is NOT captured.  The update is cut at
-    its only collective into TWO graphs - ``accumulate`` (graph construction, 2T+1 forwards, backward into the flat gradient
-    buffer) and ``apply`` (clip + AdamW + polyak) - with the RCCL all-reduce of the flat buffer issued eagerly on the same
-    stream between the two replays: the capture never depends on what the communicator does under stream capture, and a
-    rank that replays while another is still capturing cannot dead-lock inside a captured collective.
+    enc='mlp': flattened-observation batches (exp2) instead of observation graphs.
     """
 
-    def __init__(self, learner, B: int, T: int, n: int, M: int, r_comm: float = float("inf"), rew_dim: Optional[int] = None,
-                 warmup: int = 2, enc: str = "gnn"):
+    def __init__(self, learner, B: int, n: int, M: int, r_comm: float = float("inf"), warmup: int = 2, enc: str = "gnn"):
+        self.learner, self.B, self.n, self.M, self.r_comm = learner, B, n, M, r_comm
+        self._build = _builder(enc)
+        dev = learner.device
+        with_comm = learner.args.c is not None
+        self.obs = _PaddedObs((B,), n, M, dev, with_comm)
+        self.h_in = th.zeros(B * n, learner.args.hidden_size, dtype=th.float32, device=dev)
+        self._capture_act(warmup)
+
+    def _obs(self):
+        return self._build(self.obs.gt, self.obs.ubs, self.obs.agent, self.obs.d_u2u, self.r_comm, static=True)
+
+    def __call__(self, gt, ubs, agent, d_u2u, h, eps_thres: float):
+        """Copies the observation into the graph's buffers and replays.  A producer that writes ``self.obs.gt / .ubs /
+        .agent / .d_u2u`` and ``self.h_in`` in place (e.g. a device-side simulator) passes gt=None and skips the copies."""
+        if gt is not None:
+            self.obs.load(gt, ubs, agent, d_u2u)
+        return self._replay(h, eps_thres)
+
+
+def _single_ubs_enc(enc: str) -> str:
+    if enc not in ("gnn", "rnn"):
+        raise ValueError(f"enc must be 'gnn' or 'rnn', got {enc!r}")
+    return enc
+
+
+class GraphedSingleUbsAct(_GraphedActBase):
+    """``QLearner.act`` on B single-UBS environments (experiment 1) as one graph replay: the `seen-by` batch as views of the
+    observation fields (enc='gnn') or the flattened [B, 2+4M] rows filled by one copy inside the graph (enc='rnn'), no-grad policy
+    forward, epsilon-greedy selection with one draw per environment (algos/drqn/learner.py:60-63).
+
+        ga = GraphedSingleUbsAct(learner, B, M, enc, obs=(env.out["obs_gt"], env.out["obs_agent"]))
+        acts, h = ga(None, None, h, eps)                   # acts [B] int64, h' [B, H]; both are the graph's buffers
+
+    obs: (gt [B,M,4], agent [B,2]) fixed-address buffers somebody else writes - the simulator's own, so a rollout copies nothing;
+    default: buffers of the graph, filled by ``__call__(gt, agent, h, eps)``."""
+
+    def __init__(self, learner, B: int, M: int, enc: str = "gnn", obs=None, warmup: int = 2):
+        self.learner, self.B, self.M, self.enc = learner, B, M, _single_ubs_enc(enc)
+        dev = learner.device
+        f = dict(dtype=th.float32, device=dev)
+        if obs is None:
+            self.gt, self.agent = th.zeros(B, M, 4, **f), th.zeros(B, 2, **f)
+        else:
+            self.gt, self.agent = obs
+            if tuple(self.gt.shape) != (B, M, 4) or tuple(self.agent.shape) != (B, 2) or not (self.gt.is_contiguous()
+                                                                                            and self.agent.is_contiguous()):
+                raise ValueError(f"obs: contiguous gt [{B},{M},4] and agent [{B},2] expected, got {tuple(self.gt.shape)} / "
+                                 f"{tuple(self.agent.shape)}")
+        self.flat = th.zeros(B, 2 + 4 * M, **f) if enc == "rnn" else None
+        self.h_in = th.zeros(B, learner.args.hidden_size, **f)
+        self._capture_act(warmup)
+
+    def _obs(self):
+        if self.enc == "rnn":
+            return th.cat((self.agent, self.gt.view(self.B, -1)), 1, out=self.flat)
+        return from_single_ubs_obs(self.gt, self.agent)
+
+    def __call__(self, gt, agent, h, eps_thres: float):
+        """gt=None: the observation buffers were written in place (the simulator's buffers handed over as ``obs``)."""
+        if gt is not None:
+            self.gt.copy_(gt, non_blocking=True)
+            self.agent.copy_(agent, non_blocking=True)
+        return self._replay(h, eps_thres)
+
+
+class _GraphedUpdateBase:
+    """What the captured updates share: warm-up updates run for real with parameters, target, moments, ``hyper`` and the random
+    state snapshotted and restored around them, the capture of ``learner.update(self._batch())`` - cut at the gradient
+    all-reduce into two graphs when ``learner.needs_collective()`` - and the replay.  A subclass sets ``learner`` and its
+    fixed-address input buffers, defines ``_batch()`` / ``load(m)`` and calls ``_capture_update``."""
+
+    def _capture_update(self, warmup: int):
+        learner = self.learner
         assert learner.fused_tail, "graph capture needs the device-resident update tail (CUDA learner)"
-        self.learner, self.B, self.T, self.n, self.M, self.r_comm = learner, B, T, n, M, r_comm
-        self._build = _builder(enc)      # enc='mlp': flattened-observation batches (exp2)
-        dev, H = learner.device, learner.args.hidden_size
-        rd = n if rew_dim is None else rew_dim
-        # time-major: step t of every sequence is contiguous.  enc='mlp' without communication (RnnAgent) reads no talk relation
-        self.obs = _PaddedObs((T + 1, B), n, M, dev, enc == "gnn" or learner.args.c is not None)
-        self.h0 = th.zeros(B * n, H, dtype=th.float32, device=dev)
-        self.h1 = th.zeros(B * n, H, dtype=th.float32, device=dev)
-        self.acts = th.zeros(T, B * n, 1, dtype=th.int64, device=dev)
-        self.rews = th.zeros(T, B, rd, dtype=th.float32, device=dev)
-        self.dones = th.zeros(T, B, 1, dtype=th.float32, device=dev)
         self.graph = th.cuda.CUDAGraph()
         # warm-up updates run for real (they would move the parameters): snapshot and restore around them
         learner.optimizer.sync_lr()      # a learning rate the scheduler moved since the last sync is part of the snapshot, not undone by it
@@ -195,6 +236,49 @@ class GraphedUpdate:
     def _body(self) -> Dict:
         return self.learner.update(self._batch())
 
+    def __call__(self, m: Optional[Dict[str, th.Tensor]] = None) -> Dict:
+        if m is not None:
+            self.load(m)
+        self.learner.optimizer.sync_lr()
+        self.graph.replay()
+        if self.split:
+            self.learner.grads.all_reduce_mean_(self.learner.group)
+            self.graph_tail.replay()
+        self.learner.invalidate_weight_cache()   # the replay moved the parameters without passing through learner.apply()
+        return self.out
+
+
+class GraphedUpdate(_GraphedUpdateBase):
+    """``learner.update`` on B stored sequences of T transitions as one graph replay: graphs of all T+1 steps rebuilt on
+    the device from the padded observations of the sampled batch (``SequenceReplay.mem`` layout), time-batched encoder,
+    2T+1 forwards, BPTT backward, clip + AdamW + polyak.
+
+        gu = GraphedUpdate(learner, B, T, n, M, r_comm)
+        out = gu(batch)      # batch: gt [B,T+1,n,M,5], ubs, agent, d_u2u, h [B,T+1,n,H], act [B,T,n], rew [B,T,rd], done [B,T,1]
+
+    Data-parallel runs (``learner.needs_collective()``): the gradient all-reduce is NOT captured.  The update is cut at
+    its only collective into TWO graphs - ``accumulate`` (graph construction, 2T+1 forwards, backward into the flat gradient
+    buffer) and ``apply`` (clip + AdamW + polyak) - with the RCCL all-reduce of the flat buffer issued eagerly on the same
+    stream between the two replays: the capture never depends on what the communicator does under stream capture, and a
+    rank that replays while another is still capturing cannot dead-lock inside a captured collective.
+    """
+
+    def __init__(self, learner, B: int, T: int, n: int, M: int, r_comm: float = float("inf"), rew_dim: Optional[int] = None,
+                 warmup: int = 2, enc: str = "gnn"):
+        assert learner.fused_tail, "graph capture needs the device-resident update tail (CUDA learner)"
+        self.learner, self.B, self.T, self.n, self.M, self.r_comm = learner, B, T, n, M, r_comm
+        self._build = _builder(enc)      # enc='mlp': flattened-observation batches (exp2)
+        dev, H = learner.device, learner.args.hidden_size
+        rd = n if rew_dim is None else rew_dim
+        # time-major: step t of every sequence is contiguous.  enc='mlp' without communication (RnnAgent) reads no talk relation
+        self.obs = _PaddedObs((T + 1, B), n, M, dev, enc == "gnn" or learner.args.c is not None)
+        self.h0 = th.zeros(B * n, H, dtype=th.float32, device=dev)
+        self.h1 = th.zeros(B * n, H, dtype=th.float32, device=dev)
+        self.acts = th.zeros(T, B * n, 1, dtype=th.int64, device=dev)
+        self.rews = th.zeros(T, B, rd, dtype=th.float32, device=dev)
+        self.dones = th.zeros(T, B, 1, dtype=th.float32, device=dev)
+        self._capture_update(warmup)
+
     def _batch(self) -> Dict:
         T, B, n, M = self.T, self.B, self.n, self.M
         o = self.obs
@@ -218,16 +302,52 @@ class GraphedUpdate:
         self.rews.copy_(m["rew"].permute(1, 0, 2), non_blocking=True)
         self.dones.copy_(m["done"].permute(1, 0, 2), non_blocking=True)
 
-    def __call__(self, m: Optional[Dict[str, th.Tensor]] = None) -> Dict:
-        if m is not None:
-            self.load(m)
-        self.learner.optimizer.sync_lr()
-        self.graph.replay()
-        if self.split:
-            self.learner.grads.all_reduce_mean_(self.learner.group)
-            self.graph_tail.replay()
-        self.learner.invalidate_weight_cache()   # the replay moved the parameters without passing through learner.apply()
-        return self.out
+
+class GraphedSingleUbsUpdate(_GraphedUpdateBase):
+    """``QLearner.update`` on B stored sequences of T transitions of the single-UBS environment (experiment 1) as one graph replay:
+    the batch ``SingleUbsSequenceReplay.gather`` builds - T+1 per-step observation batches plus the time-batched ones, all views of
+    the graph's fixed-address buffers - then the update (time-batched encoder, recurrence, BPTT backward, clip + AdamW + polyak).
+
+        gu = GraphedSingleUbsUpdate(learner, B, T, M, enc)
+        out = gu(m)       # m: gt [B,T+1,M,4], agent [B,T+1,2], h [B,T+1,H], act / rew / done [B,T,1] (``SingleUbsSequenceReplay.mem``)
+
+    Data-parallel runs are cut at the gradient all-reduce exactly as ``GraphedUpdate`` is."""
+
+    def __init__(self, learner, B: int, T: int, M: int, enc: str = "gnn", warmup: int = 2):
+        self.learner, self.B, self.T, self.M, self.enc = learner, B, T, M, _single_ubs_enc(enc)
+        dev, H = learner.device, learner.args.hidden_size
+        f = dict(dtype=th.float32, device=dev)
+        self.gt, self.agent = th.zeros(T + 1, B, M, 4, **f), th.zeros(T + 1, B, 2, **f)          # time-major, as `gather` lays them out
+        self.flat = th.zeros(T + 1, B, 2 + 4 * M, **f) if enc == "rnn" else None
+        self.h0, self.h1 = th.zeros(B, H, **f), th.zeros(B, H, **f)
+        self.acts = th.zeros(T, B, 1, dtype=th.int64, device=dev)
+        self.rews, self.dones = th.zeros(T, B, 1, **f), th.zeros(T, B, 1, **f)
+        self._capture_update(warmup)
+
+    def _batch(self) -> Dict:
+        T, B, M = self.T, self.B, self.M
+        out = dict(h0=self.h0, h1=self.h1, acts=self.acts, rews=self.rews, dones=self.dones)
+        if self.enc == "gnn":
+            gt, agent = self.gt, self.agent
+            out["obs"] = [from_single_ubs_obs(gt[t], agent[t]) for t in range(T + 1)]
+            out["obs_all"] = from_single_ubs_obs(gt.view((T + 1) * B, M, 4), agent.view((T + 1) * B, 2))
+            out["obs_all_next"] = from_single_ubs_obs(gt[1:].view(T * B, M, 4), agent[1:].view(T * B, 2))
+        else:
+            flat = th.cat((self.agent, self.gt.view(T + 1, B, -1)), 2, out=self.flat)       # the one copy (inside the graph)
+            out["obs"] = [flat[t] for t in range(T + 1)]
+            out["obs_all"] = flat.view((T + 1) * B, -1)
+            out["obs_all_next"] = flat[1:].view(T * B, -1)
+        return out
+
+    def load(self, m: Dict[str, th.Tensor]) -> None:
+        """m: a gathered batch in ``SingleUbsSequenceReplay.mem`` layout (leading dims [B, T+1] / [B, T])."""
+        self.gt.copy_(m["gt"].transpose(0, 1), non_blocking=True)
+        self.agent.copy_(m["agent"].transpose(0, 1), non_blocking=True)
+        self.h0.copy_(m["h"][:, 0], non_blocking=True)
+        self.h1.copy_(m["h"][:, 1], non_blocking=True)
+        self.acts.copy_(m["act"].transpose(0, 1), non_blocking=True)
+        self.rews.copy_(m["rew"].transpose(0, 1), non_blocking=True)
+        self.dones.copy_(m["done"].transpose(0, 1), non_blocking=True)
 
 
 class GraphedCycle:

@@ -252,8 +252,21 @@ class MultiAgentQLearner:
             # recurrent part (comm block, GRU, head) walks the sequence.  Same arithmetic as 2T+1 separate forwards.
             N = h.shape[0]
             x_pol = self.policy_net.encode(obs_all)
+            obs_next = batch.get("obs_all_next")
+            if obs_next is None:        # a flattened [(T+1) N, F] tensor is sliced by rows, a batch of graphs by its agents
+                obs_next = obs_all[N:] if isinstance(obs_all, th.Tensor) else obs_all.slice_agents(N, (T + 1) * N)
             with th.no_grad():
-                x_tgt = self.target_net.encode(batch.get("obs_all_next") or obs_all.slice_agents(N, (T + 1) * N))
+                x_tgt = self.target_net.encode(obs_next)
+            if (hasattr(self.policy_net, "unroll") and hasattr(self.target_net, "unroll")
+                    and getattr(self.policy_net, "_comm_protocol", None) is None and h.is_cuda
+                    and ops.gru_unroll_supported(N, h.shape[1])):
+                # No communication block and few rows: nothing inside a step depends on another agent, so the input projection of
+                # the GRU and the Q head run once over all steps too, and only h W_hh^T + gates walks the sequence - one launch per
+                # step and direction (csrc/gru_rec.hip).  Same arithmetic, no per-step loop and no stack.
+                agent_out = self.policy_net.unroll(x_pol, h, T + 1)
+                with th.no_grad():
+                    target_out = self.target_net.unroll(x_tgt, h_targ, T)
+                return self._td_loss(batch, T, agent_out, target_out)
             # per-step views + the slices of ONE gradient buffer the steps' backward passes write into (no stack)
             xs, slots = ops.time_split(x_pol, T + 1)
             xt = x_tgt.view(T, N, -1)
@@ -277,8 +290,10 @@ class MultiAgentQLearner:
                     target_out.append(nxt)
             logits, h = self.policy_net(obs[T], h)
             agent_out.append(logits)
-        agent_out, target_out = th.stack(agent_out), th.stack(target_out)
+        return self._td_loss(batch, T, th.stack(agent_out), th.stack(target_out))
 
+    def _td_loss(self, batch: Dict, T: int, agent_out: th.Tensor, target_out: th.Tensor) -> tuple:
+        """learner.py:134-154 on the stacked Q values agent_out [T+1, N, n_actions] / target_out [T, N, n_actions]."""
         qvals = agent_out[:-1].gather(2, batch["acts"])
         if self.double_q:
             next_acts = agent_out[1:].detach().argmax(2, keepdim=True)

@@ -594,6 +594,85 @@ def gru_cell(inp, h, cell, rowmax=None):
     return gru_gates(gi, gh, h)
 
 
+# The recurrence of an agent WITHOUT a communication block over a whole sequence (csrc/gru_rec.hip): the input projection of all steps
+# in one GEMM, one launch per step for h W_hh^T + gates, one launch per backward step.  False: the per-step launches of `gru_cell`
+# (A/B, tools/exp1_probe.py)
+GRU_SEQ = os.environ.get("UAVGNN_GRU_SEQ", "1") != "0"
+
+
+def gru_unroll_supported(N, H) -> bool:
+    """`gru_unroll` covers N rows per step: below the row count from which the fused cells run (they win there)."""
+    return bool(GRU_SEQ and 0 < N < GRU_FUSED_MIN_ROWS and L.lib().uavgnn_gru_rec_supported(H))
+
+
+class _GruRecurrence(th.autograd.Function):
+    """h_1 .. h_T1 from the time-batched input pre-activations gi_all [T1 N, 3H] (b_ih included) and h_0 [N, H]."""
+
+    @staticmethod
+    def forward(ctx, gi_all, h0, W_hh, b_hh, T1, train):
+        L.require_gpu(gi_all, h0, W_hh, b_hh)
+        gi_all, W, b = L.f32c(gi_all), L.f32c(W_hh.detach()), L.f32c(b_hh.detach())
+        N, H = h0.shape
+        if gi_all.shape != (T1 * N, 3 * H):
+            raise L.UavGnnError(f"gru_unroll: gi_all {tuple(gi_all.shape)} is not [T1 N, 3H] = [{T1 * N}, {3 * H}]")
+        lib, st = L.lib(), L.stream()
+        # slot 0 is h_0: the h of every step is a view of the buffer its h' went into
+        hbuf = th.empty((T1 + 1, N, H), dtype=th.float32, device=h0.device)
+        hbuf[0].copy_(h0)
+        pre = th.empty((T1, N, 4 * H), dtype=th.float32, device=h0.device) if train else None
+        gi_p, h_p, pre_p = gi_all.data_ptr(), hbuf.data_ptr(), L.ptr(pre)
+        with KERNEL_TIMER.span("gru_rec_fwd", (T1, N, H)):
+            for t in range(T1):
+                rc = lib.uavgnn_gru_rec_fwd(gi_p + 12 * t * N * H, 3 * H, h_p + 4 * t * N * H, H, N, H, W.data_ptr(), b.data_ptr(),
+                                            h_p + 4 * (t + 1) * N * H, H, None if pre is None else pre_p + 16 * t * N * H, st)
+                L.check(rc, "uavgnn_gru_rec_fwd")
+        ctx.have_pre = bool(train)
+        if train:
+            ctx.save_for_backward(hbuf, pre, W)
+        ctx.T1 = T1
+        return hbuf[1:]
+
+    @staticmethod
+    def backward(ctx, d_hall):
+        if not ctx.have_pre:
+            raise L.UavGnnError("gru_unroll: backward through a forward that saved no pre-activations (train=False)")
+        hbuf, pre, W = ctx.saved_tensors
+        T1 = ctx.T1
+        N, H = hbuf.shape[1], hbuf.shape[2]
+        d_hall = L.f32c(d_hall)
+        dev = hbuf.device
+        d_gi = th.empty((T1, N, 3 * H), dtype=th.float32, device=dev)
+        d_gh = th.empty((T1, N, 3 * H), dtype=th.float32, device=dev)
+        carry = th.empty((2, N, H), dtype=th.float32, device=dev)       # step t writes carry[t & 1] and reads carry[(t + 1) & 1]
+        lib, st = L.lib(), L.stream()
+        pre_p, h_p, dh_p, gi_p, gh_p, c_p = (t.data_ptr() for t in (pre, hbuf, d_hall, d_gi, d_gh, carry))
+        with KERNEL_TIMER.span("gru_rec_bwd", (T1, N, H)):
+            for t in range(T1 - 1, -1, -1):
+                rc = lib.uavgnn_gru_rec_bwd(pre_p + 16 * t * N * H, h_p + 4 * t * N * H, H, dh_p + 4 * t * N * H,
+                                            None if t == T1 - 1 else c_p + 4 * ((t + 1) & 1) * N * H, N, H, W.data_ptr(),
+                                            gi_p + 12 * t * N * H, gh_p + 12 * t * N * H, c_p + 4 * (t & 1) * N * H, st)
+                L.check(rc, "uavgnn_gru_rec_bwd")
+        d_gh2 = d_gh.view(T1 * N, 3 * H)
+        dW = _wgrad(d_gh2, hbuf[:T1].view(T1 * N, H)) if ctx.needs_input_grad[2] else None
+        db = _colsum(d_gh2) if ctx.needs_input_grad[3] else None
+        return d_gi.view(T1 * N, 3 * H), (carry[0] if ctx.needs_input_grad[1] else None), dW, db, None, None
+
+
+def gru_unroll(x_all, h0, cell, T1):
+    """h_all [T1, N, H]: nn.GRUCell with `cell`'s parameters unrolled over the T1 time-major steps of x_all [T1 N, K] from h0 [N, H]
+    (or [1, H]).  The input projection is ONE `linear` over all steps (so are its weight, bias and input gradients), the recurrence one
+    launch per step and direction (csrc/gru_rec.hip), dW_hh / db_hh one reduction over the time-batched gate gradients."""
+    N = x_all.shape[0] // T1
+    if h0.shape[0] != N:
+        h0 = h0.expand(N, -1)
+    H = h0.shape[1]
+    if not L.lib().uavgnn_gru_rec_supported(H):
+        raise L.UavGnnError(f"gru_unroll: no instantiation for H = {H} (uavgnn_gru_rec_supported)")
+    gi_all = linear(x_all, cell.weight_ih, cell.bias_ih)
+    train = th.is_grad_enabled() and any(t.requires_grad for t in (gi_all, h0, cell.weight_hh, cell.bias_hh))
+    return _GruRecurrence.apply(gi_all, h0, cell.weight_hh, cell.bias_hh, T1, train)
+
+
 def _row_blocks(n, cap=256, min_rows=32):
     """Largest power-of-two block count <= cap that divides n with >= min_rows rows per block."""
     S = 1

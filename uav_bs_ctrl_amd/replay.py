@@ -192,10 +192,12 @@ class SingleUbsSequenceReplay:
         assert self.size >= batch_size, "Insufficient samples for update."
         return th.randperm(self.size, generator=generator, device=self.device)[:batch_size]
 
-    def gather(self, idx: th.Tensor, enc: str = "gnn") -> Dict:
+    def gather(self, idx: th.Tensor, enc: str = "gnn", time_batched: bool = True) -> Dict:
         """Batch dict in the layout ``MultiAgentQLearner.loss`` consumes (one agent per environment): obs = T+1 `seen-by`
         HeteroBatch of B environments (enc='gnn') or T+1 [B, 2+4M] tensors (enc='rnn'), h0 / h1 [B, H], acts / rews / dones
-        [T, B, 1].  The observation fields are gathered TIME-MAJOR in the one copy of the gather, so every step is a view."""
+        [T, B, 1].  The observation fields are gathered TIME-MAJOR in the one copy of the gather, so every step is a view.
+        time_batched: also obs_all / obs_all_next - all T+1 steps (the steps from 1 on) as ONE batch of (T+1) B ((T) B) environments,
+        views of the same gather - which switch on the learner's time-batched encoder and sequence-level recurrence."""
         if enc not in ("gnn", "rnn"):
             raise ValueError(f"enc must be 'gnn' or 'rnn', got {enc!r}")
         B = idx.numel()
@@ -206,12 +208,19 @@ class SingleUbsSequenceReplay:
                    acts=self.mem["act"].index_select(0, idx).transpose(0, 1).contiguous(),
                    rews=self.mem["rew"].index_select(0, idx).transpose(0, 1).contiguous(),
                    dones=self.mem["done"].index_select(0, idx).transpose(0, 1).contiguous())
+        T1 = self.T + 1
         if enc == "gnn":
-            out["obs"] = [from_single_ubs_obs(gt[t], agent[t]) for t in range(self.T + 1)]
+            out["obs"] = [from_single_ubs_obs(gt[t], agent[t]) for t in range(T1)]
+            if time_batched:
+                out["obs_all"] = from_single_ubs_obs(gt.view(T1 * B, self.M, -1), agent.view(T1 * B, -1))
+                out["obs_all_next"] = from_single_ubs_obs(gt[1:].view(self.T * B, self.M, -1), agent[1:].view(self.T * B, -1))
         else:
-            flat = th.cat((agent, gt.reshape(self.T + 1, B, -1)), 2)          # [T+1, B, 2+4M]
-            out["obs"] = [flat[t] for t in range(self.T + 1)]
+            flat = th.cat((agent, gt.reshape(T1, B, -1)), 2)                  # [T+1, B, 2+4M]
+            out["obs"] = [flat[t] for t in range(T1)]
+            if time_batched:
+                out["obs_all"] = flat.view(T1 * B, -1)
+                out["obs_all_next"] = flat[1:].view(self.T * B, -1)
         return out
 
-    def sample(self, batch_size: int, generator: Optional[th.Generator] = None, enc: str = "gnn") -> Dict:
-        return self.gather(self.sample_indices(batch_size, generator), enc)
+    def sample(self, batch_size: int, generator: Optional[th.Generator] = None, enc: str = "gnn", time_batched: bool = True) -> Dict:
+        return self.gather(self.sample_indices(batch_size, generator), enc, time_batched)
