@@ -11,9 +11,11 @@
 // environment's GTs in priority order with the UBS / RB dimension on lanes, and everything else is lane <-> GT.
 // Per-environment working set (distances, interference weights, RB table) lives in LDS.
 //
-// Tie rules: np.argsort over the <= 16 UBS distances is NumPy's small-array insertion sort, i.e. stable - reproduced.
-// np.argsort over the M average rates (next priorities) is NOT stable in NumPy (and depends on its SIMD dispatch); this
-// kernel uses the stable order (ties -> lower GT index first), see tests/test_env_sim.py for how the fixture pins it.
+// Tie rules: neither np.argsort of the reference is stable everywhere.  Over the <= 16 UBS distances it is NumPy's small-array
+// insertion sort (stable) on a CPU without a vector sort, and NumPy 2's AVX-512 sort (equal keys in the network's order) on one
+// with it; equal float32 distances need two UBSs on the same spot (both clipped into one corner).  Over the M average rates (next
+// priorities) the order of equal keys likewise depends on the SIMD dispatch.  This kernel uses the stable order in both places
+// (ties -> lower UBS / GT index first); tests/test_env_sim.py says how the fixtures pin it and keeps exact distance ties out of them.
 #include "common.h"
 
 namespace uavgnn {
