@@ -232,6 +232,33 @@ int uavgnn_eps_greedy(const float* q, int ld_q, int N, int A, int n_agents, cons
  * the rollout step replays with the current epsilon of the schedule (algos/madrqn/run.py:60-61). */
 int uavgnn_eps_greedy_dev(const float* q, int ld_q, int N, int A, int n_agents, const float* u_team, const float* u_agent,
                           const float* eps_dev, long long* acts, uavgnn_stream_t stream);
+/* The schedule itself on the device (run.py:61): *eps = (float) max(eps_end, eps_start - (eps_start - eps_end) / decay_steps * *t),
+ * evaluated in double without contraction, then *t += inc.  t: DEVICE int64 counting environment interactions; eps: the word
+ * uavgnn_eps_greedy_dev reads.  One thread, no host synchronisation.  decay_steps <= 0: UAVGNN_EINVAL. */
+int uavgnn_eps_schedule(long long* t, long long inc, double eps_start, double eps_end, double decay_steps, float* eps,
+                        uavgnn_stream_t stream);
+
+/* ---- device-resident replay state (csrc/replay.hip; reference: algos/madrqn/buffer.py:18-39) ------------------------
+ * state: DEVICE int64 {head, size}; rng: DEVICE int64 {seed, draws}; status: DEVICE int32 error bits, OR-ed in and never cleared by a
+ * kernel (bit 0: a sample asked for more sequences than the ring holds).  Every entry takes the stream, allocates nothing and
+ * never synchronises with the host, so all of them capture into a hipGraph and replay with the CURRENT counters.
+ *
+ * _commit: the E sequences under construction go to ring slots (head + e) % capacity, every field in one launch; a second
+ *   one-thread launch then sets head = (head + E) % capacity and size = min(size + E, capacity).  fields: HOST int64
+ *   [n_fields, 3] = {source base, destination base, bytes per sequence}; 16-byte accesses where the bytes and both bases are
+ *   multiples of 16, else 4-byte (no multiple of 4: UAVGNN_EINVAL).  E > capacity: UAVGNN_EINVAL before any launch.  At most 16 fields.
+ * _sample: idx [B] int64 = B distinct slots of [0, size), uniform without replacement, in ascending order, then draws += 1.
+ *   Slot s is keyed by the first word of Philox4x32-10 at counter (s, 0, draws) and key seed; the B smallest (key, slot) pairs
+ *   are taken (the rule is spelled out in csrc/replay.hip).  The result depends on (seed, draws, size, B) only.  size < B:
+ *   status |= 1 and idx[i] = i % max(size, 1).  capacity <= 65536, else UAVGNN_EUNSUPPORTED.
+ * _gather: one launch moves every field of the B sampled sequences into time-major buffers: slab_bytes bytes at
+ *   src + idx[b] src_seq_stride + t slab_bytes -> dst + t dst_step_stride + b slab_bytes for t < steps.  fields: HOST int64
+ *   [n_fields, 7] = {source base, destination base, slab_bytes, steps, src_seq_stride, dst_step_stride, sequences in the ring};
+ *   idx may hold repeats and is clamped into the ring.  Same two access widths as _commit.  At most 16 fields, B <= 65535. */
+int uavgnn_replay_commit(const long long* fields, int n_fields, int E, int capacity, long long* state, uavgnn_stream_t stream);
+int uavgnn_replay_sample(const long long* state, long long* rng, int capacity, int B, long long* idx, int32_t* status,
+                         uavgnn_stream_t stream);
+int uavgnn_replay_gather(const long long* fields, int n_fields, const long long* idx, int B, uavgnn_stream_t stream);
 
 /* ---- bias gradients ---------------------------------------------------------------------------------------------
  * acc[s, :] += column sums of the rows [s*R, (s+1)*R) of x[N, C] (row stride ld, unit column stride), R = ceil(N / S).

@@ -7,6 +7,10 @@ keeps no state (include/uavgnn.h), the device-side graph builder has a ``static`
 exploration rate / learning rate / Adam step count live in device memory, and the update's tail is one launch
 (uav_bs_ctrl_amd/optim.py) - so both calls capture into ``torch.cuda.CUDAGraph`` (hipGraph on ROCm) and replay from
 fixed-address input buffers.  Same arithmetic as the eager calls, kernel for kernel.
+
+With the replay's ring position, its sampler and the exploration schedule on the device (``replay`` with ``device_state=True``,
+csrc/replay.hip) the loop that ties the calls together captures too: ``GraphedEpisode`` replays a whole training episode - reset, rollout,
+caching, commits, sampling, gathers, updates - as one graph (``Episode``: the same launches, eager).
 """
 from __future__ import annotations
 
@@ -15,6 +19,7 @@ from typing import Dict, Optional
 import torch as th
 
 from . import _lib as L
+from . import ops
 from .graph import from_padded_obs, from_padded_obs_flat, from_single_ubs_obs
 
 
@@ -264,7 +269,9 @@ class GraphedUpdate(_GraphedUpdateBase):
     """
 
     def __init__(self, learner, B: int, T: int, n: int, M: int, r_comm: float = float("inf"), rew_dim: Optional[int] = None,
-                 warmup: int = 2, enc: str = "gnn"):
+                 warmup: int = 2, enc: str = "gnn", capture: bool = True):
+        """capture=False: only the fixed-address buffers, ``_batch()`` and ``load`` / ``load_from`` - for a larger capture that holds the
+        update itself (``GraphedEpisode``)."""
         assert learner.fused_tail, "graph capture needs the device-resident update tail (CUDA learner)"
         self.learner, self.B, self.T, self.n, self.M, self.r_comm = learner, B, T, n, M, r_comm
         self._build = _builder(enc)      # enc='mlp': flattened-observation batches (exp2)
@@ -277,7 +284,8 @@ class GraphedUpdate(_GraphedUpdateBase):
         self.acts = th.zeros(T, B * n, 1, dtype=th.int64, device=dev)
         self.rews = th.zeros(T, B, rd, dtype=th.float32, device=dev)
         self.dones = th.zeros(T, B, 1, dtype=th.float32, device=dev)
-        self._capture_update(warmup)
+        if capture:
+            self._capture_update(warmup)
 
     def _batch(self) -> Dict:
         T, B, n, M = self.T, self.B, self.n, self.M
@@ -302,6 +310,11 @@ class GraphedUpdate(_GraphedUpdateBase):
         self.rews.copy_(m["rew"].permute(1, 0, 2), non_blocking=True)
         self.dones.copy_(m["done"].permute(1, 0, 2), non_blocking=True)
 
+    def load_from(self, replay, idx: th.Tensor) -> None:
+        """The sequences ``idx`` of a device-state replay straight from its ring into the graph's buffers: ONE gather launch
+        (``replay.gather_into``) instead of one ``index_select`` and one copy per field.  Same bits as ``load``."""
+        replay.gather_into(idx, self)
+
 
 class GraphedSingleUbsUpdate(_GraphedUpdateBase):
     """``QLearner.update`` on B stored sequences of T transitions of the single-UBS environment (experiment 1) as one graph replay:
@@ -313,7 +326,8 @@ class GraphedSingleUbsUpdate(_GraphedUpdateBase):
 
     Data-parallel runs are cut at the gradient all-reduce exactly as ``GraphedUpdate`` is."""
 
-    def __init__(self, learner, B: int, T: int, M: int, enc: str = "gnn", warmup: int = 2):
+    def __init__(self, learner, B: int, T: int, M: int, enc: str = "gnn", warmup: int = 2, capture: bool = True):
+        """capture=False: only the fixed-address buffers, ``_batch()`` and ``load`` / ``load_from`` (see ``GraphedUpdate``)."""
         self.learner, self.B, self.T, self.M, self.enc = learner, B, T, M, _single_ubs_enc(enc)
         dev, H = learner.device, learner.args.hidden_size
         f = dict(dtype=th.float32, device=dev)
@@ -322,7 +336,8 @@ class GraphedSingleUbsUpdate(_GraphedUpdateBase):
         self.h0, self.h1 = th.zeros(B, H, **f), th.zeros(B, H, **f)
         self.acts = th.zeros(T, B, 1, dtype=th.int64, device=dev)
         self.rews, self.dones = th.zeros(T, B, 1, **f), th.zeros(T, B, 1, **f)
-        self._capture_update(warmup)
+        if capture:
+            self._capture_update(warmup)
 
     def _batch(self) -> Dict:
         T, B, M = self.T, self.B, self.M
@@ -348,6 +363,11 @@ class GraphedSingleUbsUpdate(_GraphedUpdateBase):
         self.acts.copy_(m["act"].transpose(0, 1), non_blocking=True)
         self.rews.copy_(m["rew"].transpose(0, 1), non_blocking=True)
         self.dones.copy_(m["done"].transpose(0, 1), non_blocking=True)
+
+    def load_from(self, replay, idx: th.Tensor) -> None:
+        """The sequences ``idx`` of a device-state replay straight from its ring into the graph's buffers: ONE gather launch
+        (``replay.gather_into``) instead of one ``index_select`` and one copy per field.  Same bits as ``load``."""
+        replay.gather_into(idx, self)
 
 
 class GraphedCycle:
@@ -393,6 +413,171 @@ class GraphedCycle:
         learner.invalidate_weight_cache()
 
     def __call__(self):
+        self.learner.optimizer.sync_lr()
+        self.graph.replay()
+        self.learner.invalidate_weight_cache()
+        return self.out
+
+
+class Episode:
+    """One whole training episode of the device loop with NO host state in it (run.py:81-99 for E parallel environments): the
+    simulator's reset, then ``episode_limit / T`` segments of T rollout steps - ``stage_obs``, the exploration schedule on the device
+    (uavgnn_eps_schedule: epsilon from a device counter of environment interactions, +E per step), the policy forward and
+    uavgnn_eps_greedy_dev, ``env.step``, ``learner.cache(..., staged=True)`` - whose last ``cache`` commits the E sequences into the
+    ring; when ``train``, ``updates_per_segment`` x (sample, gather, ``learner.update``) follow each commit.  Ring position, sampler
+    counter, exploration counter and the simulator's reset counter are all read on the device, and the per-step writes into the
+    sequences under construction walk the fixed sequence ptr = 0 .. T-1, so the same launches serve every episode: ``Episode`` runs
+    them eagerly, ``GraphedEpisode`` replays them as one graph.
+
+        ep = Episode(learner, env, replay, batch_size, eps=(1.0, 0.05, 5e4))       # replay: device_state=True, n_envs = env.B
+        out = ep()                 # {LossQ, QVals} of the last update (None when train=False); env's info tensors hold the statistics
+
+    env: ``BatchedUbsCoverageEnv.from_map(...)`` with enc 'gnn' / 'mlp' (exp3 / exp2) or ``BatchedSingleUbsCoverageEnv`` with enc
+    'gnn' / 'rnn' (exp1).  ``idx`` keeps the last sampled batch, ``eps`` / ``t`` the exploration rate and its counter."""
+
+    def __init__(self, learner, env, replay, batch_size: int, eps=(1.0, 0.05, 5e4), train: bool = True,
+                 updates_per_segment: int = 1, enc: str = "gnn"):
+        from .sim import BatchedSingleUbsCoverageEnv
+        assert learner.fused_tail, "the device loop needs the device-resident update tail (CUDA learner)"
+        self.learner, self.env, self.replay, self.batch_size = learner, env, replay, int(batch_size)
+        self.train, self.updates_per_segment, self.enc = bool(train), int(updates_per_segment), enc
+        self.single = isinstance(env, BatchedSingleUbsCoverageEnv)
+        if not getattr(replay, "device_state", False):
+            raise ValueError("replay: a device-state replay expected (device_state=True)")
+        if replay.n_envs != env.B:
+            raise ValueError(f"replay.n_envs = {replay.n_envs} but the simulator runs {env.B} environments")
+        if replay.ptr != 0:
+            raise ValueError("replay: a sequence is under construction (ptr != 0)")
+        self.T, self.E = replay.T, env.B
+        if env.episode_limit % self.T != 0:
+            raise ValueError(f"episode_limit = {env.episode_limit} is no multiple of the sequence length T = {self.T}")
+        if self.updates_per_segment < 1:
+            raise ValueError("updates_per_segment must be at least 1")
+        self.segments = env.episode_limit // self.T
+        self.eps_start, self.eps_end, self.decay_steps = (float(v) for v in eps)
+        if not self.decay_steps > 0:
+            raise ValueError("eps = (start, end, decay_steps): decay_steps must be positive")
+        dev = learner.device
+        if self.single:
+            _single_ubs_enc(enc)
+            self.upd = GraphedSingleUbsUpdate(learner, self.batch_size, self.T, env.n_gts, enc, capture=False) if self.train else None
+        else:
+            self._build = _builder(enc)
+            if env.spec is None:
+                raise ValueError("env: an environment with a map expected (BatchedUbsCoverageEnv.from_map): the reset draws on the device")
+            self.with_comm = learner.args.c is not None
+            self.with_state = replay.mem["state"].shape[-1] > 0
+            self.upd = GraphedUpdate(learner, self.batch_size, self.T, env.n_agents, env.n_gts, env.p.r_comm,
+                                     replay.mem["rew"].shape[-1], enc=enc, capture=False) if self.train else None
+        # built here, outside any capture: init_hidden moves a CPU row to the device, the scalars below are host-to-device copies
+        self.h_zero = learner.init_hidden(self.E)
+        self.eps = th.full((1,), self.eps_start, dtype=th.float32, device=dev)
+        self.t = th.zeros(1, dtype=th.int64, device=dev)
+        self.idx: Optional[th.Tensor] = None
+        self.out: Optional[Dict] = None
+
+    def _obs(self):
+        o = self.env.out
+        if self.single:
+            return o["obs_flat"] if self.enc == "rnn" else from_single_ubs_obs(o["obs_gt"], o["obs_agent"])
+        return self._build(o["obs_gt"], o["obs_ubs"], o["obs_agent"], o["d_u2u"] if self.with_comm else None, self.env.p.r_comm,
+                           static=True)
+
+    @th.no_grad()
+    def _step(self, h: th.Tensor) -> th.Tensor:
+        lr, env, rb, E = self.learner, self.env, self.replay, self.E
+        o = env.observations()
+        if self.single:
+            rb.stage_obs(dict(gt=o["gt"], agent=o["agent"], h=h))
+        else:
+            staged = dict(gt=o["gt"], ubs=o["ubs"], agent=o["agent"], d_u2u=o["d_u2u"], h=h.view(E, lr.n_agents, -1))
+            if self.with_state:
+                staged["state"] = o["state"]
+            rb.stage_obs(staged)
+        L.check(L.lib().uavgnn_eps_schedule(self.t.data_ptr(), E, self.eps_start, self.eps_end, self.decay_steps,
+                                            self.eps.data_ptr(), L.stream()), "uavgnn_eps_schedule")
+        logits, h2 = lr.policy_net(self._obs(), h)
+        N = logits.shape[0]
+        u = th.rand(E + N, device=lr.device, generator=lr._gen)
+        acts = th.empty(N, dtype=th.int64, device=lr.device)
+        logits = logits if logits.stride(1) == 1 else logits.contiguous()
+        L.check(L.lib().uavgnn_eps_greedy_dev(logits.data_ptr(), logits.stride(0), N, lr.n_actions, lr.n_agents, u.data_ptr(),
+                                              u.data_ptr() + 4 * E, self.eps.data_ptr(), acts.data_ptr(), L.stream()),
+                "uavgnn_eps_greedy_dev")
+        o2, rew, done, info = env.step(acts)
+        if self.single:
+            lr.cache(rb, None, None, acts, rew, o2, h2, done, info["BadMask"], staged=True)
+        else:
+            st = o2["state"] if self.with_state else None      # `cache` stores next_state only when a state is given (staged: not read)
+            lr.cache(rb, None, None, st, acts, rew, o2, h2, st, done, info["BadMask"], staged=True)
+        return h2
+
+    def _body(self) -> Optional[Dict]:
+        lr, env, rb = self.learner, self.env, self.replay
+        env.reset() if self.single else env.reset_from_map()
+        h, out = self.h_zero, None
+        for _ in range(self.segments):
+            with ops.frozen_weights():        # nothing moves a parameter inside a segment's rollout: weight planes are split once
+                for _ in range(self.T):
+                    h = self._step(h)
+            assert rb.ptr == 0, "the segment did not end on a commit"
+            if self.train:
+                for _ in range(self.updates_per_segment):
+                    self.idx = rb.sample_indices(self.batch_size)
+                    rb.gather_into(self.idx, self.upd)
+                    out = lr.update(self.upd._batch())
+        return out
+
+    def __call__(self) -> Optional[Dict]:
+        self.out = self._body()
+        return self.out
+
+
+class GraphedEpisode(Episode):
+    """``Episode`` as ONE graph replay: reset, every rollout step, caching, commits, sampling, gathers and updates of a whole episode
+    without host work in between (at the reference's batch sizes the loop is launch-bound: ~20 launches per ``act``, ~3000 per
+    ``update``).
+
+        ge = GraphedEpisode(learner, env, replay, batch_size, eps=(1.0, 0.05, 5e4), train=True, enc="gnn")
+        out = ge()                 # replays; the last update's {LossQ, QVals} (the graph's buffers), env.step's info tensors updated
+        replay.check()             # now and then: raises when a batch was sampled from fewer sequences than it holds
+
+    train=False: the collect-only graph for the steps before ``update_after``.  The body runs ``warmup`` times for real before the
+    capture; parameters, target, optimiser state, the random state (``_RngSnapshot``), the replay's ``state`` / ``rng`` / ``status``,
+    the exploration counter and the simulator's reset counter are restored afterwards, so a graphed run starts where an eager one
+    starts (the ring ROWS the warm-up wrote stay, beyond ``size``, where nothing samples them).  Captured on one stream without
+    forks.  Single process only: a data-parallel update holds a collective (``GraphedUpdate`` cuts the capture there).  The learning
+    rate is pushed to the device before each replay and the rollout's weight-plane store is emptied after it."""
+
+    def __init__(self, learner, env, replay, batch_size: int, eps=(1.0, 0.05, 5e4), train: bool = True,
+                 updates_per_segment: int = 1, enc: str = "gnn", warmup: int = 2):
+        assert not learner.needs_collective(), "a data-parallel update cannot be captured whole: use GraphedUpdate"
+        super().__init__(learner, env, replay, batch_size, eps, train, updates_per_segment, enc)
+        self.graph = th.cuda.CUDAGraph()
+        if hasattr(self.graph, "register_generator_state"):
+            self.graph.register_generator_state(learner._gen)
+        learner.optimizer.sync_lr()      # a learning rate the scheduler moved since the last sync is part of the snapshot, not undone by it
+        env_rng = env.rng if self.single else env.map_rng
+        state = (learner.flat.flat, learner.flat_target, learner.optimizer.m, learner.optimizer.v, learner.optimizer.hyper,
+                 replay.state, replay.rng, replay.status, self.t, self.eps, env_rng)
+        snap = [t.clone() for t in state]
+        rng = _RngSnapshot(learner)
+        side = th.cuda.Stream()
+        side.wait_stream(th.cuda.current_stream())
+        with th.cuda.stream(side):
+            for _ in range(warmup):
+                self._body()
+        th.cuda.current_stream().wait_stream(side)
+        learner.invalidate_weight_cache()
+        with _capture(self.graph):
+            self.out = self._body()
+        th.cuda.synchronize()
+        for dst, src in zip(state, snap):
+            dst.copy_(src)
+        rng.restore()
+        learner.invalidate_weight_cache()
+
+    def __call__(self) -> Optional[Dict]:
         self.learner.optimizer.sync_lr()
         self.graph.replay()
         self.learner.invalidate_weight_cache()

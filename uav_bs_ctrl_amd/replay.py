@@ -10,22 +10,129 @@ reference: T transitions per sequence plus the next observation / hidden state o
 
 Storage per sequence at 8 x 80, T = 50:  51*8*80*5*4 B = 653 KB of GT rows (+ 4 % for the rest)  ->  5 000 sequences
 (the reference's replay_size) = 3.4 GB of the 288 GB.
+
+``device_state=True`` (opt-in) moves what was left on the host - the ring position, the sampler, the batch's way into a captured update
+- to the device (csrc/replay.hip), so that a hipGraph can hold commits, samples and gathers (``graphs.GraphedEpisode``); the default keeps
+the host path as it was.
 """
 from __future__ import annotations
 
 from typing import Dict, Optional
 
+import ctypes
+
 import torch as th
 
+from . import _lib as L
 from .graph import HeteroBatch, from_obs_dicts, from_padded_obs, from_padded_obs_flat, from_single_ubs_obs, batch as hb_batch
 
 SCHEME = ("gt", "ubs", "agent", "d_u2u", "h", "state", "act", "rew", "done")
 
 
-class SequenceReplay:
+class _RingState:
+    """Ring position and sampler of both replays.  Default: Python integers ``head`` / ``size`` and ``torch.randperm`` - the host path.
+    ``device_state=True``: ``state`` int64 {head, size}, ``rng`` int64 {seed, draws} and ``status`` int32 [1] are DEVICE tensors; the
+    commit, the sampler and the gather into a captured update's buffers are one launch each (csrc/replay.hip) that read the
+    counters on the device - so a hipGraph holding them replays with the CURRENT ring position (``graphs.GraphedEpisode``).
+    A class sets ``_scheme`` (its field names) and ``mem`` / ``cur`` / ``capacity`` / ``n_envs`` / ``device`` before ``_init_ring_state``."""
+
+    def _init_ring_state(self, device_state: bool, seed: Optional[int]) -> None:
+        self.device_state = bool(device_state)
+        self.ptr = 0            # time index inside the sequences under construction (buffer.py:16)
+        self.head = 0           # next ring slot
+        self.size = 0
+        if not self.device_state:
+            if seed is not None:
+                raise ValueError("seed: the key of the device sampler (device_state=True); the host sampler takes generator=")
+            return
+        if self.device.type != "cuda":
+            raise ValueError("device_state=True: the ring counters and the sampler live on the GPU (no CPU fallback exists)")
+        if self.n_envs > self.capacity:
+            raise ValueError(f"device_state=True: one commit of n_envs = {self.n_envs} sequences exceeds capacity = {self.capacity}")
+        if seed is None:        # from torch's default generator: torch.manual_seed reproduces a run
+            seed = int(th.randint(0, 2 ** 62, (1,)).item())
+        self.head = self.size = None                          # the counters are ``state`` on the device
+        self.state = th.zeros(2, dtype=th.int64, device=self.device)
+        self.rng = th.tensor([int(seed), 0], dtype=th.int64, device=self.device)
+        self.status = th.zeros(1, dtype=th.int32, device=self.device)
+        rows = []
+        for k in self._scheme:
+            src, dst = self.cur[k], self.mem[k]
+            if src.numel() > 0:
+                rows += [src.data_ptr(), dst.data_ptr(), src[0].numel() * src.element_size()]
+        self._commit_fields = (ctypes.c_longlong * len(rows))(*rows)
+
+    def __len__(self) -> int:
+        """Committed sequences.  device_state=True: reads ``state`` from the device - a host SYNCHRONISATION (never inside a capture)."""
+        return int(self.state[1].item()) if self.device_state else self.size
+
+    def _commit(self) -> None:
+        """The E sequences under construction -> ring slots (head + e) % capacity; head and size advance (buffer.py:31)."""
+        E = self.n_envs
+        if self.device_state:
+            L.check(L.lib().uavgnn_replay_commit(self._commit_fields, len(self._commit_fields) // 3, E, self.capacity,
+                                                 self.state.data_ptr(), L.stream()), "uavgnn_replay_commit")
+            return
+        slots = (self.head + th.arange(E, device=self.device)) % self.capacity
+        for k in self._scheme:
+            self.mem[k][slots] = self.cur[k]
+        self.head = (self.head + E) % self.capacity
+        self.size = min(self.size + E, self.capacity)
+
+    def sample_indices(self, batch_size: int, generator: Optional[th.Generator] = None) -> th.Tensor:
+        """Without replacement, like ``random.sample`` (buffer.py:37-39).  device_state=True: one sampler launch keyed by the device
+        ``rng`` pair - a uniform subset in ASCENDING slot order (``random.sample`` returns a random order; the loss is a mean over
+        the batch) - no host synchronisation: asking for more than the ring holds sets ``status`` (``check()``)."""
+        if self.device_state:
+            if generator is not None:
+                raise ValueError("device_state=True: the sampler is keyed by the device `rng` pair, not by a torch generator")
+            idx = th.empty(batch_size, dtype=th.int64, device=self.device)
+            L.check(L.lib().uavgnn_replay_sample(self.state.data_ptr(), self.rng.data_ptr(), self.capacity, batch_size,
+                                                 idx.data_ptr(), self.status.data_ptr(), L.stream()), "uavgnn_replay_sample")
+            return idx
+        assert self.size >= batch_size, "Insufficient samples for update."
+        return th.randperm(self.size, generator=generator, device=self.device)[:batch_size]
+
+    def check(self) -> None:
+        """Raises when a kernel of the device-resident path flagged an error (a host synchronisation)."""
+        if self.device_state and int(self.status.item()) != 0:
+            raise L.UavGnnError(f"replay status = {int(self.status.item()):#x}: bit 0 - a batch larger than the number of committed "
+                                f"sequences was sampled (its indices were wrapped into the ring)")
+
+    def _gather_fields(self, target, B: int):
+        """[(ring tensor, first step, destination, steps)] of ``gather_into``: a class lists what its update buffers hold."""
+        raise NotImplementedError
+
+    def gather_into(self, idx: th.Tensor, target) -> None:
+        """Every field of the sampled sequences ``idx`` from the ring straight into the time-major fixed-address buffers of
+        ``target`` - a ``graphs.GraphedUpdate`` / ``GraphedSingleUbsUpdate`` or any object with their buffer attributes - in ONE
+        launch (uavgnn_replay_gather).  Same bits as ``index_select`` per field followed by ``target.load``."""
+        if not self.device_state:
+            raise ValueError("gather_into needs device_state=True")
+        if idx.dtype != th.int64 or not idx.is_contiguous():
+            raise ValueError("idx: a contiguous int64 tensor expected")
+        L.require_gpu(idx)
+        B = idx.numel()
+        rows = []
+        for name, src, t0, dst, steps in self._gather_fields(target, B):
+            slab = src[0, 0].numel()
+            if slab == 0:
+                continue
+            if dst.dtype != src.dtype or not dst.is_contiguous() or dst.numel() != steps * B * slab or not dst.is_cuda:
+                raise ValueError(f"gather_into: {name}: a contiguous {src.dtype} buffer of {steps} x {B} x {slab} elements expected, "
+                                 f"got {tuple(dst.shape)} {dst.dtype}")
+            es = src.element_size()
+            rows += [src.data_ptr() + t0 * slab * es, dst.data_ptr(), slab * es, steps, src.stride(0) * es, B * slab * es, self.capacity]
+        fields = (ctypes.c_longlong * len(rows))(*rows)
+        L.check(L.lib().uavgnn_replay_gather(fields, len(rows) // 7, idx.data_ptr(), B, L.stream()), "uavgnn_replay_gather")
+
+
+class SequenceReplay(_RingState):
+    _scheme = SCHEME
+
     def __init__(self, capacity: int, max_seq_len: int, n_agents: int, n_gts: int, hidden_size: int,
                  n_envs: int = 1, state_dim: int = 0, r_comm: float = float("inf"), rew_dim: Optional[int] = None,
-                 device="cuda"):
+                 device="cuda", device_state: bool = False, seed: Optional[int] = None):
         T, n, M = max_seq_len, n_agents, n_gts
         self.capacity, self.T, self.n, self.M, self.n_envs = capacity, T, n, M, n_envs
         self.r_comm, self.device = r_comm, th.device(device)
@@ -40,12 +147,7 @@ class SequenceReplay:
                         done=th.zeros(lead, T, 1, **f))
         self.mem = ring(capacity)
         self.cur = ring(n_envs)
-        self.ptr = 0            # time index inside the sequences under construction (buffer.py:16)
-        self.head = 0           # next ring slot
-        self.size = 0
-
-    def __len__(self) -> int:
-        return self.size
+        self._init_ring_state(device_state, seed)
 
     def push(self, tr: Dict[str, th.Tensor]) -> None:
         """One transition of every parallel env.  tr: gt/ubs/agent/d_u2u/h/state [E, ...] (observation BEFORE the action),
@@ -61,12 +163,7 @@ class SequenceReplay:
             for k in ("gt", "ubs", "agent", "d_u2u", "h", "state"):
                 if "next_" + k in tr:
                     self.cur[k][:, self.T] = tr["next_" + k]
-            E = self.n_envs
-            slots = (self.head + th.arange(E, device=self.device)) % self.capacity
-            for k in SCHEME:
-                self.mem[k][slots] = self.cur[k]
-            self.head = (self.head + E) % self.capacity
-            self.size = min(self.size + E, self.capacity)
+            self._commit()
             self.ptr = 0
 
     def stage_obs(self, tr: Dict[str, th.Tensor]) -> None:
@@ -78,10 +175,15 @@ class SequenceReplay:
             if k in tr:
                 self.cur[k][:, t] = tr[k]
 
-    def sample_indices(self, batch_size: int, generator: Optional[th.Generator] = None) -> th.Tensor:
-        """Without replacement, like ``random.sample`` (buffer.py:37-39)."""
-        assert self.size >= batch_size, "Insufficient samples for update."
-        return th.randperm(self.size, generator=generator, device=self.device)[:batch_size]
+    def _gather_fields(self, target, B: int):
+        m, o, T = self.mem, target.obs, self.T
+        out = [("gt", m["gt"], 0, o.gt, T + 1), ("ubs", m["ubs"], 0, o.ubs, T + 1), ("agent", m["agent"], 0, o.agent, T + 1)]
+        if o.d_u2u is not None:
+            out.append(("d_u2u", m["d_u2u"], 0, o.d_u2u, T + 1))
+        if getattr(target, "states", None) is not None:
+            out.append(("state", m["state"], 0, target.states, T + 1))
+        return out + [("h0", m["h"], 0, target.h0, 1), ("h1", m["h"], 1, target.h1, 1), ("act", m["act"], 0, target.acts, T),
+                      ("rew", m["rew"], 0, target.rews, T), ("done", m["done"], 0, target.dones, T)]
 
     def gather(self, idx: th.Tensor, enc: str = "gnn") -> Dict:
         """Batch dict in the layout ``MultiAgentQLearner.loss`` consumes: obs = list of T+1 HeteroBatch of B envs.
@@ -129,15 +231,17 @@ class SequenceReplay:
 SINGLE_UBS_SCHEME = ("gt", "agent", "h", "act", "rew", "done")
 
 
-class SingleUbsSequenceReplay:
+class SingleUbsSequenceReplay(_RingState):
     """The DRQN's replay of experiment 1 (algos/drqn/buffer.py:5-36, scheme ('obs', 'h', 'act', 'rew', 'done')) in HBM: a ring of
     fixed-length sequences of the single-UBS environment's observation FIELDS - gt [T+1, M, 4], agent [T+1, 2] - and the
     recurrent state h [T+1, H], plus act / rew / done [T, 1] per sequence row.  Same sequence semantics as the reference: T
     transitions, then the next observation / hidden state of the last one (buffer.py:23-25).  ``gather`` hands the learner either
     the T+1 `seen-by` batches (``from_single_ubs_obs`` on views of the gathered fields: no graph is ever stored or copied) or the
     T+1 flattened [B, 2+4M] tensors (agent || gt row-major)."""
+    _scheme = SINGLE_UBS_SCHEME
 
-    def __init__(self, capacity: int, max_seq_len: int, n_gts: int, hidden_size: int, n_envs: int = 1, device="cuda"):
+    def __init__(self, capacity: int, max_seq_len: int, n_gts: int, hidden_size: int, n_envs: int = 1, device="cuda",
+                 device_state: bool = False, seed: Optional[int] = None):
         T, M = max_seq_len, n_gts
         self.capacity, self.T, self.M, self.n_envs = capacity, T, M, n_envs
         self.device = th.device(device)
@@ -149,12 +253,7 @@ class SingleUbsSequenceReplay:
                         rew=th.zeros(lead, T, 1, **f), done=th.zeros(lead, T, 1, **f))
         self.mem = ring(capacity)
         self.cur = ring(n_envs)
-        self.ptr = 0            # time index inside the sequences under construction (buffer.py:15)
-        self.head = 0           # next ring slot
-        self.size = 0
-
-    def __len__(self) -> int:
-        return self.size
+        self._init_ring_state(device_state, seed)
 
     def push(self, tr: Dict[str, th.Tensor]) -> None:
         """One transition of every parallel env.  tr: gt / agent / h [E, ...] (observation BEFORE the action; may be absent when
@@ -170,12 +269,7 @@ class SingleUbsSequenceReplay:
             for k in ("gt", "agent", "h"):
                 if "next_" + k in tr:
                     self.cur[k][:, self.T] = tr["next_" + k]
-            E = self.n_envs
-            slots = (self.head + th.arange(E, device=self.device)) % self.capacity
-            for k in SINGLE_UBS_SCHEME:
-                self.mem[k][slots] = self.cur[k]
-            self.head = (self.head + E) % self.capacity
-            self.size = min(self.size + E, self.capacity)
+            self._commit()
             self.ptr = 0
 
     def stage_obs(self, tr: Dict[str, th.Tensor]) -> None:
@@ -187,10 +281,11 @@ class SingleUbsSequenceReplay:
             if k in tr:
                 self.cur[k][:, t] = tr[k]
 
-    def sample_indices(self, batch_size: int, generator: Optional[th.Generator] = None) -> th.Tensor:
-        """Without replacement, like ``random.sample`` (buffer.py:31-33)."""
-        assert self.size >= batch_size, "Insufficient samples for update."
-        return th.randperm(self.size, generator=generator, device=self.device)[:batch_size]
+    def _gather_fields(self, target, B: int):
+        m, T = self.mem, self.T
+        return [("gt", m["gt"], 0, target.gt, T + 1), ("agent", m["agent"], 0, target.agent, T + 1), ("h0", m["h"], 0, target.h0, 1),
+                ("h1", m["h"], 1, target.h1, 1), ("act", m["act"], 0, target.acts, T), ("rew", m["rew"], 0, target.rews, T),
+                ("done", m["done"], 0, target.dones, T)]
 
     def gather(self, idx: th.Tensor, enc: str = "gnn", time_batched: bool = True) -> Dict:
         """Batch dict in the layout ``MultiAgentQLearner.loss`` consumes (one agent per environment): obs = T+1 `seen-by`
