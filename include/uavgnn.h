@@ -238,6 +238,31 @@ int uavgnn_eps_greedy_dev(const float* q, int ld_q, int N, int A, int n_agents, 
 int uavgnn_eps_schedule(long long* t, long long inc, double eps_start, double eps_end, double decay_steps, float* eps,
                         uavgnn_stream_t stream);
 
+/* ---- evaluation episodes and epoch statistics (csrc/eval_stats.hip; reference: algos/madrqn/run.py:63-74, :115-127) ----------------
+ * _eps_greedy_philox: the selection rule of uavgnn_eps_greedy - first maximum wins, one exploration draw per team of n_agents
+ *   consecutive rows, r = min(floor(u * A), A - 1) with the product formed in float - with the uniforms drawn INSIDE the kernel, so an
+ *   evaluation never touches the host's generator and captures into a hipGraph.  rng: DEVICE int64 {seed, step}.
+ *     w(index, lane) = first output word of Philox4x32-10 (csrc/common.h) at counter (index, lane, step low word, step high word)
+ *                      under the key (seed low word, seed high word) - the keying of uavgnn_replay_sample;
+ *     u(index, lane) = (w >> 8) * 2^-24, an exact float in [0, 1);
+ *     explore(team)  = u(team, 0) <= eps                       lane 0, index = team: the exploration draw;
+ *     acts[a]        = explore(a / n_agents) ? min((int)(u(a, 1) * A), A - 1) : argmax_j q[a, j]     lane 1, index = row: the random action.
+ *   eps is *eps_dev (DEVICE, read at execution time) or, when eps_dev == NULL, the host value `eps`.  After the call, in stream order,
+ *   rng[1] = step + 1: written by a following one-thread launch, so no thread of the selection observes it.  The result depends on
+ *   (seed, step, q, N, A, n_agents, eps) only, never on the launch geometry.  UAVGNN_EINVAL for the argument errors of uavgnn_eps_greedy
+ *   (N < 0, A < 1, n_agents < 1, ld_q < A, q or acts NULL with N > 0) or rng == NULL; N == 0 launches no selection and still advances
+ *   the step.
+ * _stats_push: streaming mean / M2 / min / max of n_keys <= 16 keys in one launch, one workgroup per key.  vals: DEVICE double
+ *   [n_keys, ld], the first n values of every row are pushed; acc: DEVICE double [n_keys, 6] = {count, mean, M2, min, max, non-finite
+ *   count}, empty state {0, 0, 0, +inf, -inf, 0}.  Non-finite values are left out of the moments and of min / max and counted in
+ *   field 5; with n_b finite values of mean mean_b = sum / n_b and M2_b = sum (v - mean_b)^2 (two passes, all in double):
+ *     d = mean_b - mean, n' = count + n_b;  mean += d n_b / n';  M2 += M2_b + d^2 count n_b / n';  count = n';  min / max updated.
+ *   n_b == 0 (every value non-finite) changes field 5 only.  The reduction order is fixed: the accumulator's bits depend on the
+ *   sequence of pushes only.  n == 0: no-op.  n < 0, n_keys outside 1..16, ld < n or a NULL pointer: UAVGNN_EINVAL.  No atomics. */
+int uavgnn_eps_greedy_philox(const float* q, int ld_q, int N, int A, int n_agents, long long* rng, const float* eps_dev, float eps,
+                             long long* acts, uavgnn_stream_t stream);
+int uavgnn_stats_push(const double* vals, int ld, int n, int n_keys, double* acc, uavgnn_stream_t stream);
+
 /* ---- device-resident replay state (csrc/replay.hip; reference: algos/madrqn/buffer.py:18-39) ------------------------
  * state: DEVICE int64 {head, size}; rng: DEVICE int64 {seed, draws}; status: DEVICE int32 error bits, OR-ed in and never cleared by a
  * kernel (bit 0: a sample asked for more sequences than the ring holds).  Every entry takes the stream, allocates nothing and

@@ -10,7 +10,9 @@ fixed-address input buffers.  Same arithmetic as the eager calls, kernel for ker
 
 With the replay's ring position, its sampler and the exploration schedule on the device (``replay`` with ``device_state=True``,
 csrc/replay.hip) the loop that ties the calls together captures too: ``GraphedEpisode`` replays a whole training episode - reset, rollout,
-caching, commits, sampling, gathers, updates - as one graph (``Episode``: the same launches, eager).
+caching, commits, sampling, gathers, updates - as one graph (``Episode``: the same launches, eager).  ``Evaluation`` /
+``GraphedEvaluation`` are the reference's ``test_agent()`` on a separate evaluation simulator with their own device random state, and
+``stats=`` (``stats.EpochStats``) keeps the epoch's log row on the device.
 """
 from __future__ import annotations
 
@@ -419,7 +421,26 @@ class GraphedCycle:
         return self.out
 
 
-class Episode:
+INFO_KEYS = ("EpRet", "EpLen", "AvgGlobalUtility", "TotalThroughput", "FairIdx", "ProbCollision")
+
+
+class _EnvObs:
+    """The policy's observation batch straight from a device simulator's output buffers.  A subclass sets ``env``, ``single``, ``enc``
+    and, for the multi-UBS simulator, ``_build`` / ``with_comm``."""
+
+    def _obs(self):
+        o = self.env.out
+        if self.single:
+            return o["obs_flat"] if self.enc == "rnn" else from_single_ubs_obs(o["obs_gt"], o["obs_agent"])
+        return self._build(o["obs_gt"], o["obs_ubs"], o["obs_agent"], o["d_u2u"] if self.with_comm else None, self.env.p.r_comm,
+                           static=True)
+
+    def _info_keys(self):
+        """The statistics ``env.step`` returns (run.py:93 ``logger.store(**info)``; ProbCollision: the multi-UBS simulator only)."""
+        return tuple(k for k in INFO_KEYS if not (self.single and k == "ProbCollision"))
+
+
+class Episode(_EnvObs):
     """One whole training episode of the device loop with NO host state in it (run.py:81-99 for E parallel environments): the
     simulator's reset, then ``episode_limit / T`` segments of T rollout steps - ``stage_obs``, the exploration schedule on the device
     (uavgnn_eps_schedule: epsilon from a device counter of environment interactions, +E per step), the policy forward and
@@ -433,10 +454,14 @@ class Episode:
         out = ep()                 # {LossQ, QVals} of the last update (None when train=False); env's info tensors hold the statistics
 
     env: ``BatchedUbsCoverageEnv.from_map(...)`` with enc 'gnn' / 'mlp' (exp3 / exp2) or ``BatchedSingleUbsCoverageEnv`` with enc
-    'gnn' / 'rnn' (exp1).  ``idx`` keeps the last sampled batch, ``eps`` / ``t`` the exploration rate and its counter."""
+    'gnn' / 'rnn' (exp1).  ``idx`` keeps the last sampled batch, ``eps`` / ``t`` the exploration rate and its counter.
+
+    stats: a ``stats.EpochStats`` holding the info keys (EpRet, EpLen, AvgGlobalUtility, TotalThroughput, FairIdx, and ProbCollision for
+    the multi-UBS simulator) and, when ``train``, LossQ: the body pushes the info tensors once at the end of the episode and LossQ after
+    every update (run.py:93, :99) - launches on fixed addresses, so they replay with the graph.  None: nothing is pushed."""
 
     def __init__(self, learner, env, replay, batch_size: int, eps=(1.0, 0.05, 5e4), train: bool = True,
-                 updates_per_segment: int = 1, enc: str = "gnn"):
+                 updates_per_segment: int = 1, enc: str = "gnn", stats=None):
         from .sim import BatchedSingleUbsCoverageEnv
         assert learner.fused_tail, "the device loop needs the device-resident update tail (CUDA learner)"
         self.learner, self.env, self.replay, self.batch_size = learner, env, replay, int(batch_size)
@@ -475,13 +500,11 @@ class Episode:
         self.t = th.zeros(1, dtype=th.int64, device=dev)
         self.idx: Optional[th.Tensor] = None
         self.out: Optional[Dict] = None
-
-    def _obs(self):
-        o = self.env.out
-        if self.single:
-            return o["obs_flat"] if self.enc == "rnn" else from_single_ubs_obs(o["obs_gt"], o["obs_agent"])
-        return self._build(o["obs_gt"], o["obs_ubs"], o["obs_agent"], o["d_u2u"] if self.with_comm else None, self.env.p.r_comm,
-                           static=True)
+        self.stats, self.info = stats, None
+        if stats is not None:
+            missing = [k for k in self._info_keys() + (("LossQ",) if self.train else ()) if k not in stats.index]
+            if missing:
+                raise ValueError(f"stats: keys {missing} are missing")
 
     @th.no_grad()
     def _step(self, h: th.Tensor) -> th.Tensor:
@@ -510,6 +533,7 @@ class Episode:
         else:
             st = o2["state"] if self.with_state else None      # `cache` stores next_state only when a state is given (staged: not read)
             lr.cache(rb, None, None, st, acts, rew, o2, h2, st, done, info["BadMask"], staged=True)
+        self.info = info
         return h2
 
     def _body(self) -> Optional[Dict]:
@@ -526,6 +550,10 @@ class Episode:
                     self.idx = rb.sample_indices(self.batch_size)
                     rb.gather_into(self.idx, self.upd)
                     out = lr.update(self.upd._batch())
+                    if self.stats is not None:
+                        self.stats.push(LossQ=out["LossQ"])
+        if self.stats is not None:
+            self.stats.push(**{k: self.info[k] for k in self._info_keys()})
         return out
 
     def __call__(self) -> Optional[Dict]:
@@ -544,15 +572,15 @@ class GraphedEpisode(Episode):
 
     train=False: the collect-only graph for the steps before ``update_after``.  The body runs ``warmup`` times for real before the
     capture; parameters, target, optimiser state, the random state (``_RngSnapshot``), the replay's ``state`` / ``rng`` / ``status``,
-    the exploration counter and the simulator's reset counter are restored afterwards, so a graphed run starts where an eager one
-    starts (the ring ROWS the warm-up wrote stay, beyond ``size``, where nothing samples them).  Captured on one stream without
+    the exploration counter, the simulator's reset counter and the accumulator of ``stats`` are restored afterwards, so a graphed run
+    starts where an eager one starts (the ring ROWS the warm-up wrote stay, beyond ``size``, where nothing samples them).  Captured on one stream without
     forks.  Single process only: a data-parallel update holds a collective (``GraphedUpdate`` cuts the capture there).  The learning
     rate is pushed to the device before each replay and the rollout's weight-plane store is emptied after it."""
 
     def __init__(self, learner, env, replay, batch_size: int, eps=(1.0, 0.05, 5e4), train: bool = True,
-                 updates_per_segment: int = 1, enc: str = "gnn", warmup: int = 2):
+                 updates_per_segment: int = 1, enc: str = "gnn", warmup: int = 2, stats=None):
         assert not learner.needs_collective(), "a data-parallel update cannot be captured whole: use GraphedUpdate"
-        super().__init__(learner, env, replay, batch_size, eps, train, updates_per_segment, enc)
+        super().__init__(learner, env, replay, batch_size, eps, train, updates_per_segment, enc, stats)
         self.graph = th.cuda.CUDAGraph()
         if hasattr(self.graph, "register_generator_state"):
             self.graph.register_generator_state(learner._gen)
@@ -560,6 +588,8 @@ class GraphedEpisode(Episode):
         env_rng = env.rng if self.single else env.map_rng
         state = (learner.flat.flat, learner.flat_target, learner.optimizer.m, learner.optimizer.v, learner.optimizer.hyper,
                  replay.state, replay.rng, replay.status, self.t, self.eps, env_rng)
+        if stats is not None:
+            state += tuple(stats.state_tensors())      # the warm-up episodes' pushes are undone as well
         snap = [t.clone() for t in state]
         rng = _RngSnapshot(learner)
         side = th.cuda.Stream()
@@ -581,4 +611,159 @@ class GraphedEpisode(Episode):
         self.learner.optimizer.sync_lr()
         self.graph.replay()
         self.learner.invalidate_weight_cache()
+        return self.out
+
+
+class Evaluation(_EnvObs):
+    """The reference's ``test_agent()`` / ``load_and_run_policy`` loop (run.py:63-74, :132-178) on the device: ``episodes`` evaluation
+    episodes on the caller's EVALUATION simulator, ``env.B`` at a time, acting with a fixed exploration rate (0.05 there) and storing
+    nothing in a replay.  A call runs ``episodes / env.B`` rounds of: the simulator's reset, zero hidden state, ``episode_limit`` steps
+    of (no-grad policy forward, uavgnn_eps_greedy_philox, ``env.step``); the info tensors at the end of a round go to columns
+    r B .. (r+1) B of a [K, episodes] float64 table and, with ``stats``, into ``stats`` under ``prefix + key``.
+
+        ev = Evaluation(learner, test_env, episodes=10, eps=0.05, seed=0)
+        table = ev()               # {EpRet, EpLen, AvgGlobalUtility, TotalThroughput, FairIdx[, ProbCollision]: float64 [episodes]} (device)
+
+    It leaves the training run untouched: the uniforms come from the evaluation's own device {seed, step} (``rng``), never from
+    ``learner._gen``; the weight planes live in a store of the call's own, not in the learner's rollout store; no parameter is
+    written; every ``rng_state`` of the policy's modules (DiscreteComm's in-kernel noise counter) is copied on the device before the
+    rounds and copied back after them.  A comm module that no training forward has seeded yet seeds itself from torch's host generator
+    during the call: it is put back to unseeded and the host generator's state restored, so the training run later draws the seed it
+    would have drawn (until then every such evaluation draws the same noise).  No host state enters the launches, so
+    ``GraphedEvaluation`` replays them as one graph.
+
+    env / enc: as for ``Episode``.  ``eps`` lives in device memory (``eps``: float32 [1]) and may be refilled between calls."""
+
+    def __init__(self, learner, env, episodes: int, eps: float = 0.05, seed: int = 0, enc: str = "gnn", stats=None,
+                 prefix: str = "Test"):
+        from .sim import BatchedSingleUbsCoverageEnv
+        self.learner, self.env, self.enc, self.stats, self.prefix = learner, env, enc, stats, prefix
+        self.single = isinstance(env, BatchedSingleUbsCoverageEnv)
+        self.episodes = int(episodes)
+        if self.episodes < 1 or self.episodes % env.B != 0:
+            raise ValueError(f"episodes = {episodes} is no positive multiple of the simulator's {env.B} environments")
+        self.rounds = self.episodes // env.B
+        if self.single:
+            _single_ubs_enc(enc)
+        else:
+            self._build = _builder(enc)
+            if env.spec is None:
+                raise ValueError("env: an environment with a map expected (BatchedUbsCoverageEnv.from_map): the reset draws on the device")
+            self.with_comm = learner.args.c is not None
+        self.keys = self._info_keys()
+        if stats is not None:
+            missing = [prefix + k for k in self.keys if prefix + k not in stats.index]
+            if missing:
+                raise ValueError(f"stats: keys {missing} are missing")
+        dev = learner.device
+        self.n_agents = 1 if self.single else env.n_agents
+        # built here, outside any capture (host-to-device copies)
+        self.h_zero = learner.init_hidden(env.B)
+        self.eps = th.tensor([float(eps)], dtype=th.float32, device=dev)
+        self.rng = th.tensor([int(seed), 0], dtype=th.int64, device=dev)       # {seed, step} of the selection's uniforms
+        self.table = th.zeros(len(self.keys), self.episodes, dtype=th.float64, device=dev)
+        self.out = {k: self.table[i] for i, k in enumerate(self.keys)}
+
+    def _comm_modules(self):
+        return [m for m in self.learner.policy_net.modules() if hasattr(m, "rng_state")]
+
+    def _select(self, logits: th.Tensor) -> th.Tensor:
+        lr = self.learner
+        N = logits.shape[0]
+        acts = th.empty(N, dtype=th.int64, device=lr.device)
+        logits = logits if logits.stride(1) == 1 else logits.contiguous()
+        L.check(L.lib().uavgnn_eps_greedy_philox(logits.data_ptr(), logits.stride(0), N, lr.n_actions, self.n_agents,
+                                                 self.rng.data_ptr(), self.eps.data_ptr(), 0.0, acts.data_ptr(), L.stream()),
+                "uavgnn_eps_greedy_philox")
+        return acts
+
+    def _comm_save(self):
+        """The policy's comm ``rng_state``s before the rounds: device copies of the ones that exist; for a module that was never
+        seeded (no training forward yet) the host generator's state, which its first forward draws the seed from."""
+        mods = self._comm_modules()
+        saved = [(m, m.rng_state.clone() if isinstance(m.rng_state, th.Tensor) else None) for m in mods]
+        host = th.get_rng_state() if any(st is None for _, st in saved) else None
+        return saved, host
+
+    def _comm_restore(self, saved, host, unseed: bool = True):
+        """Copies the saved states back.  A module this evaluation seeded itself goes back to unseeded and the host generator to
+        where it stood (``unseed``), so the training run's first forward draws the seed it would have drawn without the evaluation."""
+        for m, st in saved:
+            if st is not None:
+                m.rng_state.copy_(st)
+            elif isinstance(m.rng_state, th.Tensor):
+                if unseed:
+                    m.rng_state = None
+                else:
+                    m.rng_state[1:].zero_()
+        if host is not None and unseed:
+            th.set_rng_state(host)
+
+    @th.no_grad()
+    def _rounds(self) -> None:
+        lr, env, B = self.learner, self.env, self.env.B
+        with ops.frozen_weights():            # a store of this call's own: the learner's rollout store is not touched
+            for r in range(self.rounds):
+                env.reset() if self.single else env.reset_from_map()
+                h, info = self.h_zero, None
+                for _ in range(env.episode_limit):
+                    logits, h = lr.policy_net(self._obs(), h)
+                    _, _, _, info = env.step(self._select(logits))
+                for i, k in enumerate(self.keys):
+                    self.table[i, r * B:(r + 1) * B].copy_(info[k], non_blocking=True)
+                if self.stats is not None:
+                    self.stats.push(**{self.prefix + k: info[k] for k in self.keys})
+
+    def _body(self, unseed: bool = True) -> Dict[str, th.Tensor]:
+        saved, host = self._comm_save()
+        self._rounds()
+        self._comm_restore(saved, host, unseed)
+        return self.out
+
+    def __call__(self) -> Dict[str, th.Tensor]:
+        return self._body()
+
+
+class GraphedEvaluation(Evaluation):
+    """``Evaluation`` as ONE graph replay covering all rounds.
+
+        gev = GraphedEvaluation(learner, test_env, episodes=10, stats=st)
+        table = gev()              # replays; the table rows are the graph's fixed buffers
+
+    The body runs ``warmup`` times for real on a side stream before the single-stream capture; the evaluation's {seed, step}, the
+    simulator's reset counter, the policy's comm ``rng_state``s and the accumulator of ``stats`` are restored afterwards, so a graphed
+    evaluation starts where an eager one starts.  The weight planes are rebuilt inside the graph, so a replay evaluates the CURRENT
+    parameters."""
+
+    def __init__(self, learner, env, episodes: int, eps: float = 0.05, seed: int = 0, enc: str = "gnn", stats=None,
+                 prefix: str = "Test", warmup: int = 2):
+        super().__init__(learner, env, episodes, eps, seed, enc, stats, prefix)
+        self.graph = th.cuda.CUDAGraph()
+        state = [self.rng, env.rng if self.single else env.map_rng]
+        state += [m.rng_state for m in self._comm_modules() if isinstance(m.rng_state, th.Tensor)]
+        if stats is not None:
+            state += list(stats.state_tensors())
+        snap = [t.clone() for t in state]
+        # a comm module no training forward has seeded yet is seeded by the warm-up (a host round trip the capture cannot hold) and stays
+        # seeded through the capture; afterwards the graph keeps ITS tensor (``_held``: the address it reads, saves and restores), the
+        # module goes back to unseeded and the host generator to where it stood
+        unseeded, host = self._comm_save()
+        side = th.cuda.Stream()
+        side.wait_stream(th.cuda.current_stream())
+        with th.cuda.stream(side):
+            for _ in range(max(int(warmup), 1)):     # at least once: the seeding above
+                self._body(unseed=False)
+        th.cuda.current_stream().wait_stream(side)
+        with _capture(self.graph):
+            self._body(unseed=False)
+        th.cuda.synchronize()
+        for dst, src in zip(state, snap):
+            dst.copy_(src)
+        self._held = [m.rng_state for m, st in unseeded if st is None and isinstance(m.rng_state, th.Tensor)]
+        for t in self._held:
+            t[1:].zero_()
+        self._comm_restore(unseeded, host, unseed=True)
+
+    def __call__(self) -> Dict[str, th.Tensor]:
+        self.graph.replay()
         return self.out
