@@ -263,6 +263,36 @@ int uavgnn_eps_greedy_philox(const float* q, int ld_q, int N, int A, int n_agent
                              long long* acts, uavgnn_stream_t stream);
 int uavgnn_stats_push(const double* vals, int ld, int n, int n_keys, double* acc, uavgnn_stream_t stream);
 
+/* ---- trajectory films of the evaluation simulators (csrc/film.hip; reference: envs/mubs_cov/mubs_cov.py:99-100 reload, :126-127
+ * click; envs/subs_cov/subs_cov.py:87-88 reload, :128-131 click; the two recorder.py; read back by algos/madrqn/run.py:73-74 and
+ * :132-178 and their algos/drqn twins) ------------------------------------------------------------------------------------------------
+ * ONE launch records the current step of all B environments of a simulator into a film of `episodes` episodes of T = episode_limit
+ * steps.  Environment b writes slot t[b] of episode e = episode_base + b; t is the simulator's DEVICE step counter (int32: 0 after a
+ * reset, k after the k-th step) and episode_base the only host integer, so the call captures into a hipGraph and follows the simulator.
+ *   slot 0:       film_pos_ubs[e, 0] <- pos_ubs[b] and film_pos_gts[e] <- pos_gts[b]                  (the recorder's `reload`)
+ *   slot k >= 1:  film_pos_ubs[e, k] <- pos_ubs[b] and element k - 1 of every per-step series         (the recorder's `click`)
+ * _mubs: film_pos_ubs [episodes, T+1, n, 2] f64; film_fair_idx [episodes, T] f64 <- (double) run_f32[b, 2]; film_reward [episodes, T]
+ *   f64 <- (reward[b, 0] + ... + reward[b, n-1]) / n, added in agent order in double (mubs_cov.py:127 reward.mean()); film_pos_gts
+ *   [episodes, M, 2] f32.  pos_ubs [B, n, 2] f64, pos_gts [B, M, 2] f32, run_f32 [B, 4], reward [B, n] f64: the simulator's buffers.
+ * _subs: film_pos_ubs [episodes, T+1, 2] f64; film_total_throughput / film_fair_idx / film_global_utility [episodes, T] f64 <-
+ *   run_f64[b, 0] / [b, 2] / [b, 3]; film_reward [episodes, T] f64 <- reward[b]; film_rate_per_gt [episodes, T, M] f32 <- rate_per_gt[b];
+ *   film_velocity [episodes, T] f64 <- hypot(avail_moves[actions[b]]) / dt in double (subs_cov.py:131); film_pos_gts [episodes, M, 2]
+ *   f32.  actions [B] int64: the actions of the step just taken; NULL for the call after a reset.  avail_moves [A, 2] f64.
+ * status: DEVICE int32 error bits, OR-ed in and never cleared by a kernel.  Bit 0: an environment whose t[b] is outside 0 .. T or
+ *   whose episode is outside 0 .. episodes - 1 - and, for _subs, a step slot recorded with actions == NULL or with an action outside
+ *   0 .. A - 1 - wrote NOTHING.  No store leaves the film.  Plain vector stores; the OR into status is the only atomic.
+ * UAVGNN_EINVAL before any launch: a NULL pointer (actions excepted; the GT and rate pointers only when M > 0), B < 0, n < 1, M < 0,
+ *   T < 1, A < 1, dt <= 0, episodes < 0, episode_base < 0.  B == 0: no launch. */
+int uavgnn_film_click_mubs(int B, int n, int M, int T, int episodes, int episode_base, const int32_t* t, const double* pos_ubs,
+                           const float* pos_gts, const float* run_f32, const double* reward, double* film_pos_ubs,
+                           double* film_fair_idx, double* film_reward, float* film_pos_gts, int32_t* status, uavgnn_stream_t stream);
+int uavgnn_film_click_subs(int B, int M, int T, int A, double dt, int episodes, int episode_base, const int32_t* t,
+                           const long long* actions, const double* avail_moves, const double* pos_ubs, const float* pos_gts,
+                           const double* run_f64, const double* reward, const float* rate_per_gt, double* film_pos_ubs,
+                           double* film_total_throughput, double* film_fair_idx, double* film_global_utility, double* film_reward,
+                           float* film_rate_per_gt, double* film_velocity, float* film_pos_gts, int32_t* status,
+                           uavgnn_stream_t stream);
+
 /* ---- device-resident replay state (csrc/replay.hip; reference: algos/madrqn/buffer.py:18-39) ------------------------
  * state: DEVICE int64 {head, size}; rng: DEVICE int64 {seed, draws}; status: DEVICE int32 error bits, OR-ed in and never cleared by a
  * kernel (bit 0: a sample asked for more sequences than the ring holds).  Every entry takes the stream, allocates nothing and

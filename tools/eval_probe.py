@@ -10,6 +10,10 @@
   exp1   n_grps = 4 x gts_per_grp = 5 (1 x 20, episode limit 200), 'gnn' agent, H = 256, 10 environments x 1 round
 
     python tools/eval_probe.py [--runs 3] [--out profiles/eval_probe.txt]
+    python tools/eval_probe.py --film [--runs 7] [--out profiles/eval_film_probe.txt]
+
+--film: arm (c) alone, twice in one process - without a film and with ``film=Film(env, 10)`` (one more launch per reset and per step,
+csrc/film.hip) -, the two graphs replayed alternately; per arm the launches a replay holds that the other does not.
 
 Measurements, not thresholds: host clock around one call that ends in a device synchronise, after a warm-up call of every arm; ``runs``
 runs per arm, the median reported.  One JSON row per arm; the table goes to --out (default profiles/eval_probe.txt)."""
@@ -91,26 +95,67 @@ def rows_for(name, make, runs):
     return rows
 
 
+def film_rows_for(name, make, runs):
+    """GraphedEvaluation without and with a film, both built first and then replayed alternately (the same process, the same clocks)."""
+    import torch as th
+
+    from uav_bs_ctrl_amd.film import Film
+    from uav_bs_ctrl_amd.graphs import GraphedEvaluation
+    arms = {}
+    for arm in ("c: GraphedEvaluation", "d: GraphedEvaluation(film=...)"):
+        learner, env, enc = make()
+        film = Film(env, E) if arm.startswith("d") else None
+        arms[arm] = (GraphedEvaluation(learner, env, E, eps=EPS, seed=0, enc=enc, film=film), env, film)
+        arms[arm][0]()
+    ms = {arm: [] for arm in arms}
+    for _ in range(runs):
+        for arm, (run, _, _) in arms.items():
+            th.cuda.synchronize()
+            t0 = time.perf_counter()
+            run()
+            th.cuda.synchronize()
+            ms[arm].append(1e3 * (time.perf_counter() - t0))
+    rows = []
+    for arm, (_, env, film) in arms.items():
+        if film is not None:
+            film.check()
+        rows.append(dict(what=name, arm=arm, envs=E, episode_limit=env.episode_limit, film_launches=0 if film is None else 1 + env.episode_limit,
+                         ms=[round(m, 3) for m in ms[arm]], median_ms=round(statistics.median(ms[arm]), 3)))
+        print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--runs", type=int, default=None, help="timed calls per arm (default 3; 7 with --film)")
+    ap.add_argument("--film", action="store_true", help="the graphed evaluation without and with a trajectory film")
     ap.add_argument("--points", nargs="+", default=["exp3", "exp1"])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "eval_probe.txt"), help="the rows as a table ('' for none)")
+    ap.add_argument("--out", default=None, help="the rows as a table ('' for none; default profiles/eval_probe.txt, "
+                    "profiles/eval_film_probe.txt with --film)")
     a = ap.parse_args()
+    if a.runs is None:
+        a.runs = 7 if a.film else 3
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "eval_film_probe.txt" if a.film else "eval_probe.txt")
     import torch as th
     if not th.cuda.is_available():
         raise SystemExit("eval_probe: no GPU (there is no CPU fallback)")
-    rows = []
+    rows, rows_of = [], film_rows_for if a.film else rows_for
     if "exp3" in a.points:
-        rows += rows_for("exp3: '8ubs' 8 x 50, TarMAC, H = 256", _exp3, a.runs)
+        rows += rows_of("exp3: '8ubs' 8 x 50, TarMAC, H = 256", _exp3, a.runs)
     if "exp1" in a.points:
-        rows += rows_for("exp1: 1 x 20, DRQN 'gnn', H = 256", _exp1, a.runs)
+        rows += rows_of("exp1: 1 x 20, DRQN 'gnn', H = 256", _exp1, a.runs)
     if a.out:
         with open(a.out, "w") as f:
-            f.write("evaluation probe (tools/eval_probe.py): one test_agent() of 10 episodes, MI355X, host clock around a device synchronise; "
-                    "arm (a) is the baseline\n\n")
+            if a.film:
+                f.write("evaluation film probe (tools/eval_probe.py --film): one graphed test_agent() of 10 episodes without and with a "
+                        "trajectory film, MI355X, host clock around a device synchronise, the two graphs replayed alternately\n\n")
+            else:
+                f.write("evaluation probe (tools/eval_probe.py): one test_agent() of 10 episodes, MI355X, host clock around a device "
+                        "synchronise; arm (a) is the baseline\n\n")
             for r in rows:
-                f.write(f"{r['what']:<40} {r['arm']:<30} median {r['median_ms']:>9.3f} ms   runs {r['ms']}\n")
+                extra = f"   film launches {r['film_launches']}" if a.film else ""
+                f.write(f"{r['what']:<40} {r['arm']:<32} median {r['median_ms']:>9.3f} ms   runs {r['ms']}{extra}\n")
 
 
 if __name__ == "__main__":

@@ -100,6 +100,8 @@ SIGNATURES = {
     "uavgnn_eps_schedule": (_c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_fp, _c_st]),
     "uavgnn_eps_greedy_philox": (_c_int, [_c_fp, _c_int, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_fp, _c_f32, ctypes.c_void_p, _c_st]),
     "uavgnn_stats_push": (_c_int, [ctypes.c_void_p, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_st]),
+    "uavgnn_film_click_mubs": (_c_int, [_c_int] * 6 + [_c_fp] * 10 + [_c_st]),
+    "uavgnn_film_click_subs": (_c_int, [_c_int] * 4 + [ctypes.c_double, _c_int, _c_int] + [_c_fp] * 17 + [_c_st]),
     "uavgnn_replay_commit": (_c_int, [ctypes.POINTER(ctypes.c_longlong), _c_int, _c_int, _c_int, ctypes.c_void_p, _c_st]),
     "uavgnn_replay_sample": (_c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_int, _c_int, ctypes.c_void_p, _c_ip, _c_st]),
     "uavgnn_replay_gather": (_c_int, [ctypes.POINTER(ctypes.c_longlong), _c_int, ctypes.c_void_p, _c_int, _c_st]),

@@ -632,17 +632,25 @@ class Evaluation(_EnvObs):
     would have drawn (until then every such evaluation draws the same noise).  No host state enters the launches, so
     ``GraphedEvaluation`` replays them as one graph.
 
-    env / enc: as for ``Episode``.  ``eps`` lives in device memory (``eps``: float32 [1]) and may be refilled between calls."""
+    env / enc: as for ``Episode``.  ``eps`` lives in device memory (``eps``: float32 [1]) and may be refilled between calls.
+
+    film: a ``film.Film`` of exactly ``episodes`` episodes of env's shape - the reference's ``record=True`` (run.py:73-74): every round
+    reloads it after the reset and clicks it after every step, one launch each (csrc/film.hip), so a call overwrites the film with the
+    trajectories of the episodes it just ran.  None: no such launch is issued."""
 
     def __init__(self, learner, env, episodes: int, eps: float = 0.05, seed: int = 0, enc: str = "gnn", stats=None,
-                 prefix: str = "Test"):
+                 prefix: str = "Test", film=None):
         from .sim import BatchedSingleUbsCoverageEnv
-        self.learner, self.env, self.enc, self.stats, self.prefix = learner, env, enc, stats, prefix
+        self.learner, self.env, self.enc, self.stats, self.prefix, self.film = learner, env, enc, stats, prefix, film
         self.single = isinstance(env, BatchedSingleUbsCoverageEnv)
         self.episodes = int(episodes)
         if self.episodes < 1 or self.episodes % env.B != 0:
             raise ValueError(f"episodes = {episodes} is no positive multiple of the simulator's {env.B} environments")
         self.rounds = self.episodes // env.B
+        if film is not None:
+            if film.episodes != self.episodes:
+                raise ValueError(f"film: it holds {film.episodes} episodes, the evaluation runs {self.episodes}")
+            film.match(env)
         if self.single:
             _single_ubs_enc(enc)
         else:
@@ -701,14 +709,19 @@ class Evaluation(_EnvObs):
 
     @th.no_grad()
     def _rounds(self) -> None:
-        lr, env, B = self.learner, self.env, self.env.B
+        lr, env, B, film = self.learner, self.env, self.env.B, self.film
         with ops.frozen_weights():            # a store of this call's own: the learner's rollout store is not touched
             for r in range(self.rounds):
                 env.reset() if self.single else env.reset_from_map()
+                if film is not None:
+                    film.reload(env, r * B)
                 h, info = self.h_zero, None
                 for _ in range(env.episode_limit):
                     logits, h = lr.policy_net(self._obs(), h)
-                    _, _, _, info = env.step(self._select(logits))
+                    acts = self._select(logits)
+                    _, _, _, info = env.step(acts)
+                    if film is not None:
+                        film.click(env, acts, r * B)
                 for i, k in enumerate(self.keys):
                     self.table[i, r * B:(r + 1) * B].copy_(info[k], non_blocking=True)
                 if self.stats is not None:
@@ -731,18 +744,20 @@ class GraphedEvaluation(Evaluation):
         table = gev()              # replays; the table rows are the graph's fixed buffers
 
     The body runs ``warmup`` times for real on a side stream before the single-stream capture; the evaluation's {seed, step}, the
-    simulator's reset counter, the policy's comm ``rng_state``s and the accumulator of ``stats`` are restored afterwards, so a graphed
-    evaluation starts where an eager one starts.  The weight planes are rebuilt inside the graph, so a replay evaluates the CURRENT
+    simulator's reset counter, the policy's comm ``rng_state``s, the accumulator of ``stats`` and the status word of ``film`` are restored
+    afterwards, so a graphed evaluation starts where an eager one starts.  The weight planes are rebuilt inside the graph, so a replay evaluates the CURRENT
     parameters."""
 
     def __init__(self, learner, env, episodes: int, eps: float = 0.05, seed: int = 0, enc: str = "gnn", stats=None,
-                 prefix: str = "Test", warmup: int = 2):
-        super().__init__(learner, env, episodes, eps, seed, enc, stats, prefix)
+                 prefix: str = "Test", warmup: int = 2, film=None):
+        super().__init__(learner, env, episodes, eps, seed, enc, stats, prefix, film)
         self.graph = th.cuda.CUDAGraph()
         state = [self.rng, env.rng if self.single else env.map_rng]
         state += [m.rng_state for m in self._comm_modules() if isinstance(m.rng_state, th.Tensor)]
         if stats is not None:
             state += list(stats.state_tensors())
+        if film is not None:
+            state.append(film.status)                # the film ROWS the warm-up wrote are overwritten by the first replay
         snap = [t.clone() for t in state]
         # a comm module no training forward has seeded yet is seeded by the warm-up (a host round trip the capture cannot hold) and stays
         # seeded through the capture; afterwards the graph keeps ITS tensor (``_held``: the address it reads, saves and restores), the
