@@ -458,10 +458,16 @@ class Episode(_EnvObs):
 
     stats: a ``stats.EpochStats`` holding the info keys (EpRet, EpLen, AvgGlobalUtility, TotalThroughput, FairIdx, and ProbCollision for
     the multi-UBS simulator) and, when ``train``, LossQ: the body pushes the info tensors once at the end of the episode and LossQ after
-    every update (run.py:93, :99) - launches on fixed addresses, so they replay with the graph.  None: nothing is pushed."""
+    every update (run.py:93, :99) - launches on fixed addresses, so they replay with the graph.  None: nothing is pushed.
+
+    explore_seed: None - the uniforms of the selection come from ``learner._gen`` (``th.rand`` + uavgnn_eps_greedy_dev).  An integer - the
+    selection is uavgnn_eps_greedy_philox (the same rule: one exploration draw per team, first maximum) with the schedule's device ``eps``
+    and the uniforms drawn inside the kernel from ``explore``, a device int64 {seed, step} pair of this object that advances by one per
+    step: the random state of the exploration is a plain tensor that can be saved, restored and handed from one episode object to another
+    by value (``b.explore.copy_(a.explore)``), and ``learner._gen`` is never touched."""
 
     def __init__(self, learner, env, replay, batch_size: int, eps=(1.0, 0.05, 5e4), train: bool = True,
-                 updates_per_segment: int = 1, enc: str = "gnn", stats=None):
+                 updates_per_segment: int = 1, enc: str = "gnn", stats=None, explore_seed: Optional[int] = None):
         from .sim import BatchedSingleUbsCoverageEnv
         assert learner.fused_tail, "the device loop needs the device-resident update tail (CUDA learner)"
         self.learner, self.env, self.replay, self.batch_size = learner, env, replay, int(batch_size)
@@ -498,6 +504,7 @@ class Episode(_EnvObs):
         self.h_zero = learner.init_hidden(self.E)
         self.eps = th.full((1,), self.eps_start, dtype=th.float32, device=dev)
         self.t = th.zeros(1, dtype=th.int64, device=dev)
+        self.explore = None if explore_seed is None else th.tensor([int(explore_seed), 0], dtype=th.int64, device=dev)
         self.idx: Optional[th.Tensor] = None
         self.out: Optional[Dict] = None
         self.stats, self.info = stats, None
@@ -521,12 +528,17 @@ class Episode(_EnvObs):
                                             self.eps.data_ptr(), L.stream()), "uavgnn_eps_schedule")
         logits, h2 = lr.policy_net(self._obs(), h)
         N = logits.shape[0]
-        u = th.rand(E + N, device=lr.device, generator=lr._gen)
         acts = th.empty(N, dtype=th.int64, device=lr.device)
         logits = logits if logits.stride(1) == 1 else logits.contiguous()
-        L.check(L.lib().uavgnn_eps_greedy_dev(logits.data_ptr(), logits.stride(0), N, lr.n_actions, lr.n_agents, u.data_ptr(),
-                                              u.data_ptr() + 4 * E, self.eps.data_ptr(), acts.data_ptr(), L.stream()),
-                "uavgnn_eps_greedy_dev")
+        if self.explore is not None:
+            L.check(L.lib().uavgnn_eps_greedy_philox(logits.data_ptr(), logits.stride(0), N, lr.n_actions, lr.n_agents,
+                                                     self.explore.data_ptr(), self.eps.data_ptr(), 0.0, acts.data_ptr(), L.stream()),
+                    "uavgnn_eps_greedy_philox")
+        else:
+            u = th.rand(E + N, device=lr.device, generator=lr._gen)
+            L.check(L.lib().uavgnn_eps_greedy_dev(logits.data_ptr(), logits.stride(0), N, lr.n_actions, lr.n_agents, u.data_ptr(),
+                                                  u.data_ptr() + 4 * E, self.eps.data_ptr(), acts.data_ptr(), L.stream()),
+                    "uavgnn_eps_greedy_dev")
         o2, rew, done, info = env.step(acts)
         if self.single:
             lr.cache(rb, None, None, acts, rew, o2, h2, done, info["BadMask"], staged=True)
@@ -572,15 +584,15 @@ class GraphedEpisode(Episode):
 
     train=False: the collect-only graph for the steps before ``update_after``.  The body runs ``warmup`` times for real before the
     capture; parameters, target, optimiser state, the random state (``_RngSnapshot``), the replay's ``state`` / ``rng`` / ``status``,
-    the exploration counter, the simulator's reset counter and the accumulator of ``stats`` are restored afterwards, so a graphed run
-    starts where an eager one starts (the ring ROWS the warm-up wrote stay, beyond ``size``, where nothing samples them).  Captured on one stream without
-    forks.  Single process only: a data-parallel update holds a collective (``GraphedUpdate`` cuts the capture there).  The learning
+    the exploration counter, the exploration pair of ``explore_seed``, the simulator's reset counter and the accumulator of ``stats`` are
+    restored afterwards, so a graphed run starts where an eager one starts (the ring ROWS the warm-up wrote stay, beyond ``size``, where
+    nothing samples them).  Captured on one stream without forks.  Single process only: a data-parallel update holds a collective (``GraphedUpdate`` cuts the capture there).  The learning
     rate is pushed to the device before each replay and the rollout's weight-plane store is emptied after it."""
 
     def __init__(self, learner, env, replay, batch_size: int, eps=(1.0, 0.05, 5e4), train: bool = True,
-                 updates_per_segment: int = 1, enc: str = "gnn", warmup: int = 2, stats=None):
+                 updates_per_segment: int = 1, enc: str = "gnn", warmup: int = 2, stats=None, explore_seed: Optional[int] = None):
         assert not learner.needs_collective(), "a data-parallel update cannot be captured whole: use GraphedUpdate"
-        super().__init__(learner, env, replay, batch_size, eps, train, updates_per_segment, enc, stats)
+        super().__init__(learner, env, replay, batch_size, eps, train, updates_per_segment, enc, stats, explore_seed)
         self.graph = th.cuda.CUDAGraph()
         if hasattr(self.graph, "register_generator_state"):
             self.graph.register_generator_state(learner._gen)
@@ -588,6 +600,8 @@ class GraphedEpisode(Episode):
         env_rng = env.rng if self.single else env.map_rng
         state = (learner.flat.flat, learner.flat_target, learner.optimizer.m, learner.optimizer.v, learner.optimizer.hyper,
                  replay.state, replay.rng, replay.status, self.t, self.eps, env_rng)
+        if self.explore is not None:
+            state += (self.explore,)
         if stats is not None:
             state += tuple(stats.state_tensors())      # the warm-up episodes' pushes are undone as well
         snap = [t.clone() for t in state]

@@ -9,6 +9,7 @@ tensor-native replay consume, so a rollout never leaves the GPU: simulator -> gr
     obs = env.reset(pos_ubs, pos_gts, prior)           # or env.reset() with the built-in uniform placement
     obs, reward, done, info = env.step(actions)        # actions [B, n] int64 on the device
     g = env.graph()                                    # HeteroBatch of the current observations (f1)
+    info = env.get_env_info("gnn")                     # obs_shape, state_shape, n_actions, n_agents, episode_limit: the learner's env_info
 
 Initial positions and the initial GT priority permutation are INPUTS of ``reset`` (the reference draws them from Python's /
 NumPy's global generators in ``Map.set_positions`` and ``reset``); ``reset()`` without arguments places UBSs and GTs uniformly.
@@ -312,6 +313,17 @@ class BatchedUbsCoverageEnv:
                     TotalThroughput=self.run_f32[:, 0], ProbCollision=self.n_colls / self.t.clamp(min=1),
                     BadMask=o["done"])                       # the only termination is the episode limit (:343-345)
         return self.observations(), o["reward"], o["done"], info
+
+    def get_env_info(self, enc: str = "gnn") -> dict:
+        """The wrapper's ``get_env_info`` (madrqn/utils/env_wrappers.py:114-117): enc 'gnn' -> the feature sizes of the observation
+        graph's node types (:62-63: the visibility flags of ``ubs`` / ``gt`` rows become edges, not features), 'mlp' -> the width
+        of the flattened observation (:48-49; ``graph.from_padded_obs_flat``'s row: agent, gt, ubs)."""
+        if enc not in ("gnn", "mlp"):
+            raise ValueError(f"enc must be 'gnn' or 'mlp', got {enc!r}")
+        n, M, Sg = self.n_agents, self.n_gts, self.out["obs_gt"].shape[-1]
+        obs_shape = 2 + Sg * M + 3 * max(n - 1, 0) if enc == "mlp" else dict(agent=2, ubs=2, gt=Sg - 1)
+        return dict(obs_shape=obs_shape, state_shape=self.state_dim, n_actions=self.n_actions, n_agents=n,
+                    episode_limit=self.episode_limit)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
