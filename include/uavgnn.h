@@ -321,6 +321,23 @@ int uavgnn_replay_gather(const long long* fields, int n_fields, const long long*
  * across the BPTT steps in the caller's acc[S, C]; the caller folds the S partials once per update.  Deterministic.
  */
 int uavgnn_colsum_acc(const float* x, long long ld, int N, int C, float* acc, int S, uavgnn_stream_t stream);
+/* ---- QMIX mixing tail (csrc/qmix.hip; reference: algos/madrqn/agents/mixers.py:31-45 under learner.py:145-148) ------------------
+ * proj [rows, (n+3) e] (row stride ld_proj floats) is the stacked hyper-network projection of agents/qmix.py with the column blocks
+ * w1 [n e, agent-major] | w_final [e] | b1 [e] | v_hid [e]; qs [rows, n] contiguous; v2w [e], v2b [1]: the weight and bias of V[2].
+ *   pre_j = sum_i qs_i |w1_ij| + b1_j,  hid_j = elu(pre_j),  q_tot = sum_j hid_j |wf_j| + sum_j relu(vh_j) v2w_j + v2b
+ * fp32 VALU, dword accesses only (no alignment asked of any operand), deterministic, no atomics.  1 <= n <= 16 and 1 <= e <= 128, else
+ * UAVGNN_EUNSUPPORTED; a NULL operand is UAVGNN_EINVAL; rows == 0 returns 0 without a launch.
+ * _fwd (mixers.py:31-45): q_tot [rows]; nothing else is written or saved.
+ * _bwd (mixers.py:31-45 under loss.backward()): recomputes pre / hid and writes d_proj [rows, (n+3) e] (row stride ld_dproj; every
+ *   element of the four blocks, with sign(0) = 0 for the two abs and [vh > 0] for the ReLU), d_qs [rows, n] and partials [G, e+1]:
+ *   row g of it holds workgroup g's sums over its rows of d_qtot relu(vh_j) (columns 0..e-1: d v2w) and of d_qtot (column e: d v2b);
+ *   the caller sums the G rows in a fixed order.  G must be what _bwd_partials returns for (rows, e), else UAVGNN_EINVAL.
+ * _bwd_partials (mixers.py:31-45): G, a function of the shape only (never of the device), at least 1. */
+int uavgnn_qmix_mix_fwd(const float* proj, long long ld_proj, const float* qs, const float* v2w, const float* v2b, int rows, int n, int e,
+                        float* q_tot, uavgnn_stream_t stream);
+int uavgnn_qmix_mix_bwd(const float* proj, long long ld_proj, const float* qs, const float* d_qtot, const float* v2w, int rows, int n,
+                        int e, float* d_proj, long long ld_dproj, float* d_qs, float* partials, int G, uavgnn_stream_t stream);
+int uavgnn_qmix_mix_bwd_partials(int rows, int e);
 /* ---- dense layers on the f16 matrix cores, exactly scaled two-term splits (csrc/gemm_h2.hip, round 6) -----------------------------
  * Y = [X (K1 columns) || X2 (K - K1 columns; NULL: one source, K1 = K)] B^T (+ bias) (+ Y) (ReLU): the products of
  * uavgnn_gemm_nt_x3 / _cat with THREE f16 x f16 MFMA products per fp32 product instead of six bf16 ones (arithmetic, error and

@@ -106,6 +106,10 @@ SIGNATURES = {
     "uavgnn_replay_sample": (_c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_int, _c_int, ctypes.c_void_p, _c_ip, _c_st]),
     "uavgnn_replay_gather": (_c_int, [ctypes.POINTER(ctypes.c_longlong), _c_int, ctypes.c_void_p, _c_int, _c_st]),
     "uavgnn_colsum_acc": (_c_int, [_c_fp, ctypes.c_longlong, _c_int, _c_int, _c_fp, _c_int, _c_st]),
+    "uavgnn_qmix_mix_fwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_fp, _c_st]),
+    "uavgnn_qmix_mix_bwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_fp, ctypes.c_longlong, _c_fp,
+                                     _c_fp, _c_int, _c_st]),
+    "uavgnn_qmix_mix_bwd_partials": (_c_int, [_c_int, _c_int]),
     "uavgnn_relu_bwd_colsum": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_int, _c_int, _c_fp,
                                _c_int, _c_st]),
     "uavgnn_relu_bwd_colsum_rowmax": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_int, _c_int,

@@ -262,6 +262,7 @@ class GraphedUpdate(_GraphedUpdateBase):
 
         gu = GraphedUpdate(learner, B, T, n, M, r_comm)
         out = gu(batch)      # batch: gt [B,T+1,n,M,5], ubs, agent, d_u2u, h [B,T+1,n,H], act [B,T,n], rew [B,T,rd], done [B,T,1]
+                             # with learner.mixer (QMIX): also state [B,T+1,state_dim] -> ``self.states`` [T+1,B,state_dim], rd = 1
 
     Data-parallel runs (``learner.needs_collective()``): the gradient all-reduce is NOT captured.  The update is cut at
     its only collective into TWO graphs - ``accumulate`` (graph construction, 2T+1 forwards, backward into the flat gradient
@@ -286,6 +287,9 @@ class GraphedUpdate(_GraphedUpdateBase):
         self.acts = th.zeros(T, B * n, 1, dtype=th.int64, device=dev)
         self.rews = th.zeros(T, B, rd, dtype=th.float32, device=dev)
         self.dones = th.zeros(T, B, 1, dtype=th.float32, device=dev)
+        # QMIX (learner.py:145-148): the global state of all T+1 steps; None without a mixer (``SequenceReplay._gather_fields`` looks here)
+        mixer = getattr(learner, "mixer", None)
+        self.states = None if mixer is None else th.zeros(T + 1, B, mixer.state_dim, dtype=th.float32, device=dev)
         if capture:
             self._capture_update(warmup)
 
@@ -298,11 +302,14 @@ class GraphedUpdate(_GraphedUpdateBase):
         flat = lambda x, lo: x[lo:].reshape((-1,) + x.shape[2:])  # noqa: E731
         obs_all = build(flat(o.gt, 0), flat(o.ubs, 0), flat(o.agent, 0), None, self.r_comm, static=True)
         obs_next = build(flat(o.gt, 1), flat(o.ubs, 1), flat(o.agent, 1), None, self.r_comm, static=True)
-        return dict(obs=obs, obs_all=obs_all, obs_all_next=obs_next, h0=self.h0, h1=self.h1, acts=self.acts,
-                    rews=self.rews, dones=self.dones)
+        out = dict(obs=obs, obs_all=obs_all, obs_all_next=obs_next, h0=self.h0, h1=self.h1, acts=self.acts,
+                   rews=self.rews, dones=self.dones)
+        if self.states is not None:
+            out["states"] = self.states
+        return out
 
     def load(self, m: Dict[str, th.Tensor]) -> None:
-        """m: a gathered batch in ``SequenceReplay.mem`` layout (leading dims [B, T+1] / [B, T])."""
+        """m: a gathered batch in ``SequenceReplay.mem`` layout (leading dims [B, T+1] / [B, T]; ``state`` [B, T+1, state_dim] with a mixer)."""
         B, T, n = self.B, self.T, self.n
         self.obs.load(m["gt"].transpose(0, 1), m["ubs"].transpose(0, 1), m["agent"].transpose(0, 1),
                       m["d_u2u"].transpose(0, 1))
@@ -311,6 +318,8 @@ class GraphedUpdate(_GraphedUpdateBase):
         self.acts.copy_(m["act"].permute(1, 0, 2).reshape(T, B * n, 1), non_blocking=True)
         self.rews.copy_(m["rew"].permute(1, 0, 2), non_blocking=True)
         self.dones.copy_(m["done"].permute(1, 0, 2), non_blocking=True)
+        if self.states is not None:
+            self.states.copy_(m["state"].transpose(0, 1), non_blocking=True)
 
     def load_from(self, replay, idx: th.Tensor) -> None:
         """The sequences ``idx`` of a device-state replay straight from its ring into the graph's buffers: ONE gather launch
@@ -455,6 +464,8 @@ class Episode(_EnvObs):
 
     env: ``BatchedUbsCoverageEnv.from_map(...)`` with enc 'gnn' / 'mlp' (exp3 / exp2) or ``BatchedSingleUbsCoverageEnv`` with enc
     'gnn' / 'rnn' (exp1).  ``idx`` keeps the last sampled batch, ``eps`` / ``t`` the exploration rate and its counter.
+    A learner with ``mixer=True`` (QMIX) trains here as well: the replay must store the simulator's ``state`` at the mixer's width and ONE
+    shared reward (``state_dim=env.state_dim, rew_dim=1``, ``args.share_reward``), else ``ValueError``.
 
     stats: a ``stats.EpochStats`` holding the info keys (EpRet, EpLen, AvgGlobalUtility, TotalThroughput, FairIdx, and ProbCollision for
     the multi-UBS simulator) and, when ``train``, LossQ: the body pushes the info tensors once at the end of the episode and LossQ after
@@ -498,6 +509,14 @@ class Episode(_EnvObs):
                 raise ValueError("env: an environment with a map expected (BatchedUbsCoverageEnv.from_map): the reset draws on the device")
             self.with_comm = learner.args.c is not None
             self.with_state = replay.mem["state"].shape[-1] > 0
+            if getattr(learner, "mixer", None) is not None:      # QMIX: q_tot is one value per environment, mixed from the stored global state
+                sd, rd = replay.mem["state"].shape[-1], replay.mem["rew"].shape[-1]
+                if sd != learner.mixer.state_dim:
+                    raise ValueError(f"replay: the mixer reads a state of width {learner.mixer.state_dim} but the replay stores "
+                                     f"state_dim = {sd}")
+                if rd != 1:
+                    raise ValueError(f"replay: the mixer's q_tot is one value per environment (share_reward) but the replay stores "
+                                     f"rew_dim = {rd}")
             self.upd = GraphedUpdate(learner, self.batch_size, self.T, env.n_agents, env.n_gts, env.p.r_comm,
                                      replay.mem["rew"].shape[-1], enc=enc, capture=False) if self.train else None
         # built here, outside any capture: init_hidden moves a CPU row to the device, the scalars below are host-to-device copies

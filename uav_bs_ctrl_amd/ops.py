@@ -998,6 +998,57 @@ def linear(x, W, b=None):
     return _LinearSplitK.apply(x, W, b)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# QMIX mixing tail (csrc/qmix.hip): everything of the mixer behind its hyper-network GEMM in one launch per direction
+# ---------------------------------------------------------------------------------------------------------------------
+QMIX_MAX_AGENTS, QMIX_MAX_EMBED = 16, 128
+
+
+class _QmixMix(th.autograd.Function):
+    """q_tot [rows] of mixers.py:31-45 from the stacked projection proj [rows, (n+3) e] and qs [rows, n].  The forward saves its inputs
+    only; the backward recomputes the hidden layer (one launch) and sums the per-workgroup partials of d V[2] in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, proj, qs, v2w, v2b):
+        L.require_gpu(proj, qs, v2w, v2b)
+        proj, qs, v2w, v2b = L.f32c(proj), L.f32c(qs), L.f32c(v2w), L.f32c(v2b)
+        rows, n = qs.shape
+        e = v2w.numel()
+        q_tot = th.empty(rows, dtype=th.float32, device=proj.device)
+        with KERNEL_TIMER.span("qmix_mix_fwd", (rows, n, e)):
+            rc = L.lib().uavgnn_qmix_mix_fwd(proj.data_ptr(), proj.stride(0), qs.data_ptr(), v2w.data_ptr(), v2b.data_ptr(), rows, n, e,
+                                             q_tot.data_ptr(), L.stream())
+        L.check(rc, "uavgnn_qmix_mix_fwd")
+        ctx.save_for_backward(proj, qs, v2w)
+        ctx.v2w_shape, ctx.v2b_shape = v2w.shape, v2b.shape
+        return q_tot
+
+    @staticmethod
+    def backward(ctx, d_qtot):
+        proj, qs, v2w = ctx.saved_tensors
+        lib = L.lib()
+        rows, n = qs.shape
+        e = v2w.numel()
+        d_qtot = L.f32c(d_qtot)
+        d_proj, d_qs = th.empty_like(proj), th.empty_like(qs)
+        G = lib.uavgnn_qmix_mix_bwd_partials(rows, e)
+        part = th.empty((G, e + 1), dtype=th.float32, device=proj.device)
+        if rows == 0:
+            part.zero_()
+        with KERNEL_TIMER.span("qmix_mix_bwd", (rows, n, e)):
+            rc = lib.uavgnn_qmix_mix_bwd(proj.data_ptr(), proj.stride(0), qs.data_ptr(), d_qtot.data_ptr(), v2w.data_ptr(), rows, n, e,
+                                         d_proj.data_ptr(), d_proj.stride(0), d_qs.data_ptr(), part.data_ptr(), G, L.stream())
+        L.check(rc, "uavgnn_qmix_mix_bwd")
+        tot = part.sum(0)
+        return d_proj, d_qs, tot[:e].reshape(ctx.v2w_shape), tot[e:].reshape(ctx.v2b_shape)
+
+
+def qmix_mix(proj, qs, v2_weight, v2_bias):
+    """proj [rows, (n+3) e], qs [rows, n], v2_weight [e] or [1, e], v2_bias [1] -> q_tot [rows]; CUDA float32,
+    n <= QMIX_MAX_AGENTS, e <= QMIX_MAX_EMBED (the caller checks: ``agents.qmix.QMixer.forward``)."""
+    return _QmixMix.apply(proj, qs, v2_weight, v2_bias)
+
+
 RELU_BWD_FUSED = os.environ.get("UAVGNN_RELU_BWD_FUSED", "1") != "0"   # ReLU mask + bias gradient in one pass (A/B switch)
 
 

@@ -284,7 +284,8 @@ class Run:
         self.exp, self.single, self.seeds, self.save_replay = exp, exp == "exp1", seeds, bool(ours["save_replay"])
         E_test = int(ours["n_test_envs"])
         if getattr(args, "mixer", False):
-            raise ValueError("mixer = True is not covered: the episode's update buffers (graphs.GraphedUpdate) gather no state batch")
+            raise ValueError("mixer = True is not covered by the driver yet: graphs.Episode / GraphedEpisode train with a mixer, "
+                             "Run does not build one")
         if E < 1 or E_test < 1 or int(args.num_test_episodes) % E_test != 0:
             raise ValueError(f"n_test_envs = {E_test} must divide num_test_episodes = {args.num_test_episodes} (n_envs = {E}: positive)")
         spec = _env_from_config(ours["env"])
