@@ -289,9 +289,41 @@ def drqn_gnn_agent_forward(g: dict, h, p: dict, n_heads: int):
 # --------------------------------------------------------------------------------------------------------------------
 # row L: the BPTT pattern of MultiAgentQLearner.update (learner.py:110-154), loss only (no optimiser).
 
+# f4: QMixer.forward (mixers.py:31-45), restated from the formula at the head of csrc/qmix.hip
+
+def qmixer(qs, states, p: dict, signs=None):
+    """Monotonic mixing network.  qs [..., n], states [..., S] (same leading dimensions), p: state_dict of the reference module
+    (hyper_w_1, hyper_w_final, hyper_b_1: one Linear each on the state; V: Linear - ReLU - Linear) -> q_tot [..., 1]:
+        w1 = |hyper_w_1(s)| as [n, e] (agent-major)      hidden = elu(qs w1 + hyper_b_1(s))
+        w_final = |hyper_w_final(s)|                     q_tot = hidden . w_final + V(s)
+    ``signs``: dict(w1=, w_final=, v_hid=) of sign patterns {-1, 0, 1} / a 0-1 mask, shaped like the three projections.  Where given,
+    |x| is evaluated as x * sign and relu(x) as x * mask: the two kinks of the mixer taken at a PRESCRIBED branch (madrqn_loss)."""
+    n = qs.shape[-1]
+    lead = qs.shape[:-1]
+    s2, q2 = states.reshape(-1, states.shape[-1]), qs.reshape(-1, 1, n)
+    e = p["hyper_w_final.weight"].shape[0]
+    signs = signs or {}
+
+    def mag(x, key):
+        return x.abs() if signs.get(key) is None else x * signs[key].to(x.dtype).reshape(x.shape)
+    w1 = mag(F.linear(s2, p["hyper_w_1.weight"], p["hyper_w_1.bias"]), "w1").view(-1, n, e)
+    b1 = F.linear(s2, p["hyper_b_1.weight"], p["hyper_b_1.bias"]).view(-1, 1, e)
+    hidden = F.elu(th.bmm(q2, w1) + b1)
+    w_final = mag(F.linear(s2, p["hyper_w_final.weight"], p["hyper_w_final.bias"]), "w_final").view(-1, e, 1)
+    v_hid = F.linear(s2, p["V.0.weight"], p["V.0.bias"])
+    v_hid = th.relu(v_hid) if signs.get("v_hid") is None else v_hid * signs["v_hid"].to(v_hid.dtype).reshape(v_hid.shape)
+    v = F.linear(v_hid, p["V.2.weight"], p["V.2.bias"]).view(-1, 1, 1)
+    return (th.bmm(hidden, w_final) + v).view(*lead, 1)
+
+
 def madrqn_loss(obs, h0, h1, acts, rews, dones, p_policy, p_target, cfg, gamma, double_q=True, next_acts=None, gumbels=None,
-                hard_bits=None):
+                hard_bits=None, mixer=None, mixer_signs=None):
     """obs: list of T+1 graph dicts; acts [T, B*n, 1] long; rews/dones broadcastable to [T, B, n].
+
+    ``mixer`` (learner.py:145-148): (mixer parameters, target-mixer parameters, states [T+1, B, S]) - the chosen Q values of a team
+    are mixed into one value per (t, b) by ``qmixer`` on states[:-1], the target values by the target mixer on states[1:]; rews / dones
+    are then the team's [T, B, 1].  ``mixer_signs``: the ``signs`` of the POLICY mixer's call (the target mixer is not differentiated
+    and both of its kinks are continuous in value).
 
     ``next_acts`` [T, B*n, 1] long: the double-Q action choice handed in instead of the argmax over this run's own policy
     outputs (learner.py:138 takes it from ``agent_out[1:].detach()``).  The argmax is the one discontinuous step of the loss:
@@ -326,5 +358,10 @@ def madrqn_loss(obs, h0, h1, acts, rews, dones, p_policy, p_target, cfg, gamma, 
         next_vals = target_out.max(2, keepdim=True)[0]
     shp = rews.shape[:2] + (-1,)
     qvals, next_vals = qvals.view(*shp), next_vals.view(*shp)
+    if mixer is not None:
+        p_mix, p_mix_target, states = mixer
+        qvals = qmixer(qvals, states[:-1], p_mix, mixer_signs)
+        with th.no_grad():
+            next_vals = qmixer(next_vals, states[1:], p_mix_target)
     target = rews + gamma * (1 - dones) * next_vals
     return F.mse_loss(qvals, target.expand_as(qvals)), agent_out, target_out

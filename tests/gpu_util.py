@@ -118,14 +118,23 @@ class _LibSpy:
         return call
 
 
-def _exp3_learner_and_sequence(B, n, M, T, dist, seed, c="tarmac"):
+def _exp3_learner_and_sequence(B, n, M, T, dist, seed, c="tarmac", mixer=False):
     """exp3 learner whose target network differs from the policy (as it does after the first polyak step) and whose biases
-    are not DGL's zeros, + one sampled batch of bench.py's generator.  c: the communication variant of run_exp3.py's grid."""
+    are not DGL's zeros, + one sampled batch of bench.py's generator.  c: the communication variant of run_exp3.py's grid.
+    mixer: QMIX on top (embed_dim = 32, madrqn/config.py) - mixer and target mixer treated like the two networks, ``states``
+    [T + 1, B, S] of the simulator's state size in the batch, rews / dones in the team form [T, B, 1] ``_td_loss`` expands."""
+    import copy
+
     import bench
+    from uav_bs_ctrl_amd import _lib as L
     from uav_bs_ctrl_amd.learner import MultiAgentQLearner
     th.manual_seed(seed)
-    learner = MultiAgentQLearner(dict(obs_shape=dict(agent=2, ubs=2, gt=4), n_actions=9, n_agents=n, episode_limit=T),
-                                 bench.exp3_args("cuda", c=c))
+    args, env_info = bench.exp3_args("cuda", c=c), dict(obs_shape=dict(agent=2, ubs=2, gt=4), n_actions=9, n_agents=n, episode_limit=T)
+    if mixer:
+        args = copy.copy(args)
+        args.mixer, args.embed_dim = True, 32
+        env_info["state_shape"] = L.lib().uavgnn_env_state_dim(n, M, 0)
+    learner = MultiAgentQLearner(env_info, args)
     gen = th.Generator(device="cuda").manual_seed(1000 + seed)
     with th.no_grad():
         for prm in learner.policy_net.parameters():
@@ -136,6 +145,15 @@ def _exp3_learner_and_sequence(B, n, M, T, dist, seed, c="tarmac"):
     learner.invalidate_weight_cache()
     batch = bench.make_sequence(B, n, M, T, dist, th.device("cuda"), seed=7 + seed, distinct=2)
     batch["h0"] = 0.1 * th.randn(B * n, 256, device="cuda", generator=gen)          # stored hidden states, not zeros
+    if mixer:
+        with th.no_grad():
+            for prm in learner.mixer.parameters():
+                if prm.dim() == 1:
+                    prm.add_(0.05 * th.randn(prm.shape, device="cuda", generator=gen))
+            for pt, pp in zip(learner.target_mixer.parameters(), learner.mixer.parameters()):
+                pt.copy_(pp + 0.02 * pp.abs().mean() * th.randn(pp.shape, device="cuda", generator=gen))
+        batch["states"] = th.randn(T + 1, B, env_info["state_shape"], device="cuda", generator=gen)
+        batch["rews"], batch["dones"] = batch["rews"].mean(2, keepdim=True), batch["dones"][:, :, :1].contiguous()
     return learner, batch
 
 
@@ -158,17 +176,25 @@ class _ScriptedRelu:
         return th.nn.functional.relu(x) if m is None else x * m.to(x.dtype).view_as(x)
 
 
-def _oracle_update(learner, batch, dtype, next_acts=None, relu_masks=None, cfg=None, gumbels=None, hard_bits=None, disc_logits=None):
+def _oracle_update(learner, batch, dtype, next_acts=None, relu_masks=None, cfg=None, gumbels=None, hard_bits=None, disc_logits=None,
+                   mixer_signs=None):
     """loss, policy outputs, the gradient of every policy parameter and the ReLU pre-activations (in call order) from
     oracle/restatement.py:madrqn_loss on the CPU.  cfg: the oracle's configuration (default EXP3); gumbels / hard_bits: DiscreteComm's
     per-forward noise and hard-bit override (R.madrqn_loss); disc_logits: a list that receives the per-EDGE logits [E, 2 msg] of every
-    DiscreteComm forward, in call order."""
+    DiscreteComm forward, in call order.  A learner with a mixer: the oracle mixes with its parameters and ``batch["states"]``
+    (R.madrqn_loss ``mixer``; mixer_signs: the prescribed branch of the policy mixer's kinks), and the gradients of the mixer's
+    parameters follow under ``"mixer." + name``."""
     cfg = dict(EXP3) if cfg is None else dict(cfg)
     pp = {k: v.detach().cpu().to(dtype).requires_grad_(True) for k, v in learner.policy_net.state_dict().items()}
     pt = {k: v.detach().cpu().to(dtype) for k, v in learner.target_net.state_dict().items()}
     obs = [_oracle_obs(g, dtype) for g in batch["obs"]]
     f = lambda t: t.detach().cpu().to(dtype)   # noqa: E731
     script, real, real_dc = _ScriptedRelu(relu_masks), R.F, R.disc_comm
+    mix, pm = {}, {}
+    if getattr(learner, "mixer", None) is not None:
+        pm = {k: v.detach().cpu().to(dtype).requires_grad_(True) for k, v in learner.mixer.state_dict().items()}
+        pmt = {k: v.detach().cpu().to(dtype) for k, v in learner.target_mixer.state_dict().items()}
+        mix = dict(mixer=(pm, pmt, f(batch["states"])), mixer_signs=mixer_signs)
 
     def disc_spy(g, x, h, p, *a, **k):
         disc_logits.append(R.disc_logits(x, h, p).detach().index_select(0, R.talk_edges(g)[0]))
@@ -178,11 +204,13 @@ def _oracle_update(learner, batch, dtype, next_acts=None, relu_masks=None, cfg=N
         R.disc_comm = disc_spy
     try:
         loss, agent_out, _ = R.madrqn_loss(obs, f(batch["h0"]), f(batch["h1"]), batch["acts"].cpu(), f(batch["rews"]), f(batch["dones"]),
-                                           pp, pt, cfg, learner.gamma, True, next_acts=next_acts, gumbels=gumbels, hard_bits=hard_bits)
+                                           pp, pt, cfg, learner.gamma, True, next_acts=next_acts, gumbels=gumbels, hard_bits=hard_bits,
+                                           **mix)
     finally:
         R.F, R.disc_comm = real, real_dc
     names = [k for k, _ in learner.policy_net.named_parameters()]
-    return loss.detach(), agent_out.detach(), dict(zip(names, th.autograd.grad(loss, [pp[k] for k in names]))), script.pre
+    grads = th.autograd.grad(loss, [pp[k] for k in names] + list(pm.values()))
+    return loss.detach(), agent_out.detach(), dict(zip(names + ["mixer." + k for k in pm], grads)), script.pre
 
 
 def _gpu_relu_patterns(learner, batch, T, N):
@@ -210,7 +238,35 @@ def _gpu_relu_patterns(learner, batch, T, N):
 UPDATE_CASES = [("1280 rows", 160, 8, 20, 3), ("4096 rows", 512, 8, 10, 2), ("16384 rows", 2048, 8, 6, 1)]
 
 
-def _oracle_at_gpu_branch(learner, batch, q_gpu, T, N, what, cfg=None, disc=None, stats=None):
+def _mixer_branch(learner, batch, proj_gpu, what, st):
+    """The ``signs`` of R.qmixer as the HIP path took them: the signs of the w1 | w_final blocks and the ReLU mask of the v_hid block of
+    the fp32 projection ``ops.qmix_mix`` was handed for the policy mixer ([T B, (n + 3) e], CPU).  Asserted on the way: float64's own
+    pattern - from its own projection of the same states - differs only where float64 itself sits on the kink (|proj64| <= 1e-5 of the
+    tensor's scale) and on at most 1e-5 of the elements + 2, the rule for the encoder's ReLUs above."""
+    mix = learner.mixer
+    n, e = mix.n_agents, mix.embed_dim
+    sd = {k: v.detach().cpu().double() for k, v in mix.state_dict().items()}
+    heads = ("hyper_w_1", "hyper_w_final", "hyper_b_1", "V.0")
+    s2 = batch["states"][:-1].detach().cpu().double().reshape(-1, mix.state_dim)
+    proj64 = th.nn.functional.linear(s2, th.cat([sd[h + ".weight"] for h in heads], 0), th.cat([sd[h + ".bias"] for h in heads], 0))
+    assert proj_gpu.shape == proj64.shape, f"{what}: projection {tuple(proj_gpu.shape)} vs {tuple(proj64.shape)}"
+    assert_close(proj_gpu, proj64, 1e-5, f"{what}: hyper-network projection")
+
+    def pattern(p):
+        return th.cat([p[:, :(n + 1) * e].sign(), (p[:, (n + 2) * e:] > 0).to(p.dtype)], 1)
+    pat_gpu, pat64 = pattern(proj_gpu.double()), pattern(proj64)
+    under = th.cat([proj64[:, :(n + 1) * e], proj64[:, (n + 2) * e:]], 1)       # the elements under an abs or the ReLU
+    flipped = pat_gpu != pat64
+    st["mixer_total"], st["mixer_flips"], st["mixer_margin"] = under.numel(), int(flipped.sum()), 0.0
+    if bool(flipped.any()):
+        worst, scale = float(under[flipped].abs().max()), float(proj64.abs().max())
+        assert worst <= 1e-5 * scale, f"{what}: the mixer's sign / ReLU pattern differs from float64's away from the kink ({worst:.3e} of {scale:.3e})"
+        st["mixer_margin"] = worst / scale
+    assert st["mixer_flips"] <= 1e-5 * under.numel() + 2, f"{what}: {st['mixer_flips']} sign / ReLU elements of the mixer flipped"
+    return dict(w1=pat_gpu[:, :n * e], w_final=pat_gpu[:, n * e:(n + 1) * e], v_hid=pat_gpu[:, (n + 1) * e:])
+
+
+def _oracle_at_gpu_branch(learner, batch, q_gpu, T, N, what, cfg=None, disc=None, stats=None, mixer_proj=None):
     """(loss, Q values, gradients) of the float64 oracle and (loss, gradients) of the float32 oracle for ONE batch, evaluated at the
     branch the HIP path took.  The loss has two kinds of DISCONTINUITIES, at which an fp32 and a float64 evaluation may legitimately part:
     the double-Q argmax (learner.py:138) and the ReLU kinks of the encoder (one flipped element of 3 x 10^6 moves a gradient by
@@ -224,7 +280,11 @@ def _oracle_at_gpu_branch(learner, batch, q_gpu, T, N, what, cfg=None, disc=None
     third discontinuity: float64 is evaluated AT the kernel's bits, and at every forward its own choice from its own logits must differ
     from the kernel's only where |(l0 + g0) - (l1 + g1)| <= 2e-5 of the forward's logit scale (max |logit|).  stats: a dict that
     receives, per kind of decision (argmax / relu / bits), how many were taken at the HIP path's branch against float64's own choice
-    and the largest float64 margin among them relative to the scale it was judged against."""
+    and the largest float64 margin among them relative to the scale it was judged against.
+
+    mixer_proj (a learner with a mixer): the fp32 projection the HIP path handed ``ops.qmix_mix`` for the POLICY mixer.  The |.| of its
+    w1 / w_final blocks and the ReLU of its v_hid block are two more kinks of the gradient: handled as the encoder's ReLUs
+    (``_mixer_branch``), and the gradients of the mixer's parameters come back under ``"mixer." + name``."""
     hb = None if disc is None else disc["bits"]
     gum = lambda dt: None if disc is None else [g.to(dt) for g in disc["gumbels"]]   # noqa: E731
     trace = None if disc is None else []
@@ -265,11 +325,12 @@ def _oracle_at_gpu_branch(learner, batch, q_gpu, T, N, what, cfg=None, disc=None
                 st["bits"] += int(other.sum())
                 st["bits_margin"] = max(st["bits_margin"], worst / scale)
         assert st["bits"] <= 1e-5 * st["bits_total"] + 2, f"{what}: {st['bits']} hard bits differ from float64's"
+    signs = None if mixer_proj is None else _mixer_branch(learner, batch, mixer_proj, what, st)
     if stats is not None:
         stats.update(st)
-    if flips or bool(diff.any()):
+    if flips or bool(diff.any()) or st.get("mixer_flips"):
         l64, q64, g64, _ = _oracle_update(learner, batch, th.float64, next_acts=na_gpu, relu_masks=patterns, cfg=cfg, gumbels=gum(th.float64),
-                                          hard_bits=hb)
+                                          hard_bits=hb, mixer_signs=signs)
     l32, _, g32, _ = _oracle_update(learner, batch, th.float32, next_acts=na_gpu, relu_masks=patterns, cfg=cfg, gumbels=gum(th.float32),
-                                    hard_bits=hb)
+                                    hard_bits=hb, mixer_signs=signs)
     return l64, q64, g64, l32, g32

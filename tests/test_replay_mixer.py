@@ -74,6 +74,64 @@ def test_qmixer_matches_reference_fixture():
         assert_close(g, th.as_tensor(z["grad:" + k]), 1e-10, f"grad {k}", floor=1e-14)
 
 
+def test_oracle_qmixer_matches_reference_fixture():
+    """oracle/restatement.py:qmixer (the float64 side of tests/test_learner_qmix_gpu.py) against the same fixture, value and every
+    gradient - free, and with its two kinks prescribed at the branch its own projections take (the same function there)."""
+    from oracle import restatement as R
+    z = np.load(f"{GOLDEN}/qmixer.npz")
+    import ast
+    shapes = [ast.literal_eval(str(s)) for s in z["param_shapes"]]
+    names = [str(k) for k in z["param_names"]]
+    p = {k: closed_form_tensor(s, 1.0 + i * math.pi / 7, 0.1 if len(s) == 1 else 0.25, th.float64).requires_grad_(True)
+         for i, (k, s) in enumerate(zip(names, shapes))}
+    states = th.as_tensor(z["states"])
+    lin = lambda m: th.nn.functional.linear(states.reshape(-1, states.shape[-1]), p[m + ".weight"], p[m + ".bias"]).detach()  # noqa: E731
+    signs = dict(w1=lin("hyper_w_1").sign(), w_final=lin("hyper_w_final").sign(), v_hid=lin("V.0") > 0)
+    for tag, sg in (("free", None), ("prescribed", signs)):
+        qs = th.as_tensor(z["qs"]).requires_grad_(True)
+        y = R.qmixer(qs, states, p, sg)
+        assert_close(y, th.as_tensor(z["y"]), 1e-12, f"{tag}: q_tot")
+        grads = th.autograd.grad((y * th.as_tensor(z["w"])).sum(), [p[k] for k in names] + [qs])
+        for k, g in zip(names + ["__qs__"], grads):
+            assert_close(g, th.as_tensor(z["grad:" + k]), 1e-10, f"{tag}: grad {k}", floor=1e-14)
+
+
+def test_oracle_loss_with_a_mixer_reproduces_the_reference_update_fixture():
+    """oracle/restatement.py:madrqn_loss with its ``mixer`` argument against what the reference learner computed with mixer=True
+    (tests/golden/learner_update_qmix.npz, a float32 run): the loss at 1e-5 and - the fixture in the place of the code under test -
+    the mixer's gradients and the agent's (stored after the clip) under ``grad_close`` around the float64 oracle, with the float32
+    oracle for the error floor."""
+    import ast
+    from oracle import restatement as R
+    from tests.util import grad_close
+    z = np.load(f"{GOLDEN}/learner_update_qmix.npz")
+    cfg = ast.literal_eval(str(z["cfg"]))
+
+    def run(dtype):
+        def params(names, shapes):
+            out = {}
+            for i, (k, s) in enumerate(zip(names, shapes)):
+                s = ast.literal_eval(str(s))
+                out[str(k)] = closed_form_tensor(s, 1.0 + i * math.pi / 7, 0.1 if len(s) == 1 else 0.25, th.float64).to(dtype).requires_grad_(True)
+            return out
+        pp, pm = params(z["param_names"], z["param_shapes"]), params(z["mixer_param_names"], z["mixer_param_shapes"])
+        pt, pmt = {k: v.detach() for k, v in pp.items()}, {k: v.detach() for k, v in pm.items()}
+        obs = [{k.split(":")[1]: th.as_tensor(z[k]) for k in z.files if k.startswith(f"t{t}:")} for t in range(cfg["T"] + 1)]
+        obs = [{k: (v.to(dtype) if v.is_floating_point() else v) for k, v in g.items()} for g in obs]
+        f = lambda k: th.as_tensor(z[k]).to(dtype)   # noqa: E731
+        loss, _, _ = R.madrqn_loss(obs, f("h0"), f("h1"), th.as_tensor(z["acts"]).long(), f("rews"), f("dones"), pp, pt, cfg, cfg["gamma"],
+                                   cfg["double_q"], mixer=(pm, pmt, f("states")))
+        keys = [("policy", k) for k in pp] + [("mixer", k) for k in pm]
+        grads = th.autograd.grad(loss, list(pp.values()) + list(pm.values()))
+        return loss.detach(), {k: (g.clamp(-1, 1) if k[0] == "policy" else g) for k, g in zip(keys, grads)}
+    l64, g64 = run(th.float64)
+    _, g32 = run(th.float32)
+    assert_close(th.as_tensor(z["loss"]), l64, 1e-5, "LossQ")
+    assert len(g64) == len(z["param_names"]) + 10
+    for k in g64:
+        grad_close(th.as_tensor(z[f"grad:{k[0]}:{k[1]}"]), g64[k], f"reference QMIX update vs oracle: {k[0]} grad {k[1]}", ref32=g32[k])
+
+
 def test_sequence_replay_reproduces_the_reference_replay_buffer():
     """Row f2 against the reference's own ReplayBuffer (buffer.py:7-42) as filled by its learner.cache
     (learner.py:82-92) in a rollout crossing an episode end (tests/golden/replay_buffer.npz, make_golden.py `replay`):
