@@ -12,7 +12,15 @@ loops alternating, epoch by epoch, in one process.
 An epoch is ``--episodes`` training replays + one evaluation; every timed epoch trains (the collect-only replay falls into the warm-up
 epoch).  The driver's epoch also writes its row and ``state.pt`` (ring included: ``--ring`` sequences); that part is timed by itself and
 reported next to the total.  Measurements, not thresholds: host clock around work that ends in a device synchronise; spread = max - min
-over the repeats.  One JSON row per arm; --out also writes them as a table."""
+over the repeats.  One JSON row per arm; --out also writes them as a table.
+
+    python tools/train_probe.py --dp [--episodes 8] [--repeats 4] [--out profiles/train_probe.txt]
+
+--dp: what cutting the episode graph at the gradient all-reduce costs.  One epoch of exp3 at the sizes above on two runs of one process,
+alternating epoch by epoch: a non-distributed ``Run`` (every training episode ONE graph) against a ``Run`` in a world-size-1 process group
+with ``force_collective`` (every training episode cut into ``segments * updates_per_segment + 1`` graphs with the RCCL all-reduce of the
+flat gradient buffer issued eagerly at each cut).  Both with ``save_replay=False``, so ``state.pt`` is the small file in either arm.  RCCL
+at N > 1 is not what this measures.  --out APPENDS these rows to the table."""
 import argparse
 import json
 import os
@@ -164,30 +172,92 @@ def point_rows(point, episodes, repeats, ring, out_dir):
     return rows
 
 
+def dp_rows(episodes, repeats, ring, out_dir):
+    """The whole-episode graph against the graphs cut at the all-reduce (world size 1 over RCCL), alternating in this process."""
+    import socket
+
+    import torch as th
+    import torch.distributed as dist
+
+    from uav_bs_ctrl_amd.run import Run
+    env_spec, limit = _env("exp3")
+    args = _args("exp3", episodes, limit, ring)
+    kw = dict(exp_name="train_probe", seed=0, n_envs=E, n_test_envs=TEST_EPISODES, save_replay=False)
+    whole = Run.create("exp3", env_spec, args, os.path.join(out_dir, "whole"), **kw)       # built BEFORE the group exists: not data-parallel
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
+    th.cuda.set_device(0)
+    dist.init_process_group("nccl", device_id=th.device("cuda", 0))
+    try:
+        cut = Run.create("exp3", env_spec, args, os.path.join(out_dir, "cut"), force_collective=True, **kw)
+        pieces = dict(whole=len(whole.train_episode.graphs), cut=len(cut.train_episode.graphs))
+        runs = dict(whole=whole, cut=cut)
+        for run in runs.values():
+            run.train(epochs=1)                  # warm-up epoch: the collect-only replay, allocator pools, the communicator
+        wall = dict(whole=[], cut=[])
+        for _ in range(repeats):
+            for name, run in runs.items():
+                th.cuda.synchronize()
+                t0 = time.perf_counter()
+                run.train(epochs=1)
+                th.cuda.synchronize()
+                wall[name].append(1e3 * (time.perf_counter() - t0))
+        for run in runs.values():
+            run.logger.close()
+    finally:
+        dist.destroy_process_group()
+    what = (f"exp3 --dp: {episodes} training replays + 1 evaluation per epoch, {E} environments, ring {ring}, state.pt without the ring; "
+            f"world size 1")
+    arms = (("whole", "Run.train, not distributed: one graph per episode"),
+            ("cut", "Run.train, force_collective over RCCL: cut graphs"))
+    rows = [dict(what=what, arm=f"{label} ({pieces[name]} piece{'s' if pieces[name] > 1 else ''})", pieces=pieces[name],
+                 ms=[round(x, 2) for x in wall[name]], spread_ms=round(max(wall[name]) - min(wall[name]), 2)) for name, label in arms]
+    for r in rows:
+        print(json.dumps(r), flush=True)
+    return rows
+
+
+def _write_table(f, rows):
+    what = None
+    for r in rows:
+        if r["what"] != what:
+            what = r["what"]
+            f.write(f"\n{what}\n")
+        f.write(f"  {r['arm']:<42} {r['ms']}  spread {r['spread_ms']}\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--episodes", type=int, default=8, help="training replays per epoch")
     ap.add_argument("--repeats", type=int, default=4)
     ap.add_argument("--ring", type=int, default=8 * E, help="replay_size in sequences")
     ap.add_argument("--points", nargs="+", default=["exp3", "exp1"])
-    ap.add_argument("--out", default=None, help="also write the rows as a table")
+    ap.add_argument("--out", default=None, help="also write the rows as a table (--dp: append them to it)")
+    ap.add_argument("--dp", action="store_true", help="exp3 only: the whole-episode graph against the graphs cut at the gradient all-reduce")
     a = ap.parse_args()
+    if a.dp:
+        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # before the first HIP call, as bench.py sets it for RCCL
     import torch as th
     if not th.cuda.is_available():
         raise SystemExit("train_probe: no GPU (there is no CPU fallback)")
     rows = []
+    if a.dp:
+        with tempfile.TemporaryDirectory() as d:
+            rows = dp_rows(a.episodes, a.repeats, a.ring, d)
+        if a.out:
+            with open(a.out, "a") as f:
+                _write_table(f, rows)
+        return
     with tempfile.TemporaryDirectory() as d:
         for point in a.points:
             rows += point_rows(point, a.episodes if point == "exp3" else max(a.episodes // 4, 1), a.repeats, a.ring, d)
     if a.out:
         with open(a.out, "w") as f:
             f.write("train probe (tools/train_probe.py): MI355X, host clock around a device synchronise, the two loops alternating; ms per epoch\n")
-            what = None
-            for r in rows:
-                if r["what"] != what:
-                    what = r["what"]
-                    f.write(f"\n{what}\n")
-                f.write(f"  {r['arm']:<42} {r['ms']}  spread {r['spread_ms']}\n")
+            _write_table(f, rows)
 
 
 if __name__ == "__main__":

@@ -567,6 +567,11 @@ class Episode(_EnvObs):
         self.info = info
         return h2
 
+    def _update(self, batch) -> Dict:
+        """One gradient step of the body.  Data-parallel: ``learner.update`` holds the run's only collective, the all-reduce of the flat
+        gradient buffer between ``accumulate`` and ``apply`` - the one place ``GraphedEpisode`` cuts its capture."""
+        return self.learner.update(batch)
+
     def _body(self) -> Optional[Dict]:
         lr, env, rb = self.learner, self.env, self.replay
         env.reset() if self.single else env.reset_from_map()
@@ -580,7 +585,7 @@ class Episode(_EnvObs):
                 for _ in range(self.updates_per_segment):
                     self.idx = rb.sample_indices(self.batch_size)
                     rb.gather_into(self.idx, self.upd)
-                    out = lr.update(self.upd._batch())
+                    out = self._update(self.upd._batch())
                     if self.stats is not None:
                         self.stats.push(LossQ=out["LossQ"])
         if self.stats is not None:
@@ -605,16 +610,26 @@ class GraphedEpisode(Episode):
     capture; parameters, target, optimiser state, the random state (``_RngSnapshot``), the replay's ``state`` / ``rng`` / ``status``,
     the exploration counter, the exploration pair of ``explore_seed``, the simulator's reset counter and the accumulator of ``stats`` are
     restored afterwards, so a graphed run starts where an eager one starts (the ring ROWS the warm-up wrote stay, beyond ``size``, where
-    nothing samples them).  Captured on one stream without forks.  Single process only: a data-parallel update holds a collective (``GraphedUpdate`` cuts the capture there).  The learning
-    rate is pushed to the device before each replay and the rollout's weight-plane store is emptied after it."""
+    nothing samples them).  Captured on one stream without forks.  The learning rate is pushed to the device before each replay and the
+    rollout's weight-plane store is emptied after it.
+
+    Data-parallel runs (``learner.needs_collective()`` at construction, ``train=True``): the gradient all-reduce is NOT captured.  The body
+    is cut at every update into ``segments * updates_per_segment + 1`` graphs that share the first one's memory pool (``graphs``) - rollout,
+    commits, sample, gather and ``learner.accumulate`` | ``learner.apply``, the LossQ push, the next rollout ... up to the next
+    ``accumulate`` | ... - and a call replays them in order with ``learner.grads.all_reduce_mean_(learner.group)`` issued eagerly on the
+    same stream between two pieces (``collectives_per_replay`` of them), as ``GraphedUpdate`` does for one update.  The warm-up episodes
+    run their collectives eagerly, so every rank must construct the object at the same point of its program.  Without a collective, and
+    with ``train=False`` (no update), the episode is ONE graph: ``graphs == [graph]``."""
 
     def __init__(self, learner, env, replay, batch_size: int, eps=(1.0, 0.05, 5e4), train: bool = True,
                  updates_per_segment: int = 1, enc: str = "gnn", warmup: int = 2, stats=None, explore_seed: Optional[int] = None):
-        assert not learner.needs_collective(), "a data-parallel update cannot be captured whole: use GraphedUpdate"
         super().__init__(learner, env, replay, batch_size, eps, train, updates_per_segment, enc, stats, explore_seed)
-        self.graph = th.cuda.CUDAGraph()
-        if hasattr(self.graph, "register_generator_state"):
-            self.graph.register_generator_state(learner._gen)
+        collective = learner.needs_collective()
+        self.split = self.train and collective
+        self.collectives_per_replay = self.segments * self.updates_per_segment if self.split else 0
+        self._window = None                # the open capture window while the cut body is being captured
+        self.graph = self._new_graph()
+        self.graphs = [self.graph]
         learner.optimizer.sync_lr()      # a learning rate the scheduler moved since the last sync is part of the snapshot, not undone by it
         env_rng = env.rng if self.single else env.map_rng
         state = (learner.flat.flat, learner.flat_target, learner.optimizer.m, learner.optimizer.v, learner.optimizer.hyper,
@@ -632,17 +647,54 @@ class GraphedEpisode(Episode):
                 self._body()
         th.cuda.current_stream().wait_stream(side)
         learner.invalidate_weight_cache()
-        with _capture(self.graph):
-            self.out = self._body()
+        if collective:
+            th.cuda.synchronize()          # the warm-up episodes' all-reduces are complete before a capture window opens
+        if self.split:
+            self._window = _capture(self.graph)
+            self._window.__enter__()
+            try:
+                self.out = self._body()    # `_update` closes the window after each `accumulate` and opens the next graph's
+            except BaseException:
+                import sys
+                self._window.__exit__(*sys.exc_info())
+                raise
+            else:
+                self._window.__exit__(None, None, None)
+            finally:
+                self._window = None
+            assert len(self.graphs) == self.collectives_per_replay + 1
+        else:
+            with _capture(self.graph):
+                self.out = self._body()
         th.cuda.synchronize()
         for dst, src in zip(state, snap):
             dst.copy_(src)
         rng.restore()
         learner.invalidate_weight_cache()
 
+    def _new_graph(self):
+        graph = th.cuda.CUDAGraph()
+        if hasattr(graph, "register_generator_state"):
+            graph.register_generator_state(self.learner._gen)
+        return graph
+
+    def _update(self, batch) -> Dict:
+        if self._window is None:           # warm-up, or a run without a collective: the whole update
+            return super()._update(batch)
+        out = self.learner.accumulate(batch)
+        self._window.__exit__(None, None, None)      # the cut: this graph ends on the gradient, the next begins with `apply`
+        self.graphs.append(self._new_graph())
+        self._window = _capture(self.graphs[-1], pool=self.graph.pool())
+        self._window.__enter__()
+        self.learner.apply()
+        return out
+
     def __call__(self) -> Optional[Dict]:
         self.learner.optimizer.sync_lr()
         self.graph.replay()
+        for graph in self.graphs[1:]:      # data-parallel: the all-reduce of the flat gradient buffer, eagerly, at every cut
+            self.learner.grads.all_reduce_mean_(self.learner.group)
+            graph.replay()
         self.learner.invalidate_weight_cache()
         return self.out
 

@@ -5,10 +5,16 @@ log rows, checkpoints, trajectory films and resume.
     run.train()                          # all remaining epochs; run.train(epochs=k): k more
     run = Run.resume("data/exp3_8ubs_s0")    # rebuilds everything from config.json + state.pt and goes on, bit for bit
     python -m uav_bs_ctrl_amd.run --exp exp3 --env 8ubs --args-json args.json --out data/exp3_8ubs_s0 [--seed 0 --envs 32 --resume --eager]
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node N -m uav_bs_ctrl_amd.run ...     # data-parallel: N ranks, one GPU each
 
 This is host orchestration over launches that exist: a collect-only and a training ``graphs.GraphedEpisode``, one
 ``graphs.GraphedEvaluation`` with a ``film.Film``, one ``stats.EpochStats``.  It adds no launch and no host synchronisation to an
 episode or to an evaluation; per epoch it adds one ``EpochStats.summary()`` copy, ``replay.check()``, ``film.check()`` and file I/O.
+
+Data-parallel over a ``torch.distributed`` process group: every rank runs this driver on its own environments, ring
+and sampler; the training episode is a list of graphs cut at each update's gradient all-reduce.  Rank 0 evaluates and writes the
+directory, rank r >= 1 writes ``state.rank{r}.pt`` only; per epoch every rank adds one all-gather of the statistics (``stats.merge_acc``),
+one of a parameter checksum (``ReplicasDiverged``) and a barrier between writing and renaming the state files.
 
 The run directory is the reference's (utils/logx.py): ``config.json``, ``progress.txt`` (tab-separated, the reference's columns),
 ``checkpoint_epoch{k}.pt`` (``learner.save_checkpoint``: the reference's keys, for interchange), ``epoch{k}_episode{n}/`` (``Film.write``)
@@ -55,6 +61,10 @@ class RunDirectoryError(RuntimeError):
     """``Run.resume`` refuses the directory; the message says why."""
 
 
+class ReplicasDiverged(RuntimeError):
+    """A data-parallel run whose ranks no longer hold the same parameters, bit for bit: raised on every rank at the end of the epoch."""
+
+
 # ---- arguments and the plan -------------------------------------------------------------------------------------------------------------
 def check_args(exp: str, args) -> SimpleNamespace:
     """A namespace copy of ``args`` (a namespace or a dict) holding every key ``exp`` needs; ``mixer`` forces ``share_reward``
@@ -76,9 +86,9 @@ def check_args(exp: str, args) -> SimpleNamespace:
 
 class Plan(NamedTuple):
     total_steps: int            # run.py:55
-    update_after_eff: int       # run.py:56: max(update_after, batch_size * T)
+    update_after_eff: int       # run.py:56: max(update_after, world * batch_size * T)
     update_every: int           # run.py:57: T
-    steps_per_episode: int      # interactions of one episode replay: E * episode_limit
+    steps_per_episode: int      # interactions of one episode replay on all ranks: world * E * episode_limit
     episodes_per_epoch: int     # ceil(steps_per_epoch / steps_per_episode)
     interacts_per_epoch: int    # what an epoch actually runs: episodes_per_epoch * steps_per_episode
     epochs: int
@@ -88,16 +98,19 @@ class Plan(NamedTuple):
         return interactions_before < self.update_after_eff
 
 
-def plan(args, E: int, episode_limit: int, T: int) -> Plan:
-    """The numbers of run.py:55-57 and their counterparts for E environments that end their episodes together.  Pure host arithmetic."""
+def plan(args, E: int, episode_limit: int, T: int, world: int = 1) -> Plan:
+    """The numbers of run.py:55-57 and their counterparts for E environments that end their episodes together on each of ``world``
+    data-parallel ranks: interactions count all ranks, and training starts once EVERY rank's ring holds a batch (``world * batch_size *
+    T`` interactions).  Pure host arithmetic on values that are equal on all ranks, so they switch from collecting to training on the
+    same episode replay."""
     g = (lambda k: args[k]) if isinstance(args, dict) else (lambda k: getattr(args, k))
-    E, episode_limit, T = int(E), int(episode_limit), int(T)
-    if E < 1 or episode_limit < 1 or T < 1:
-        raise ValueError("plan: E, episode_limit and T must be positive")
-    per_episode = E * episode_limit
+    E, episode_limit, T, world = int(E), int(episode_limit), int(T), int(world)
+    if E < 1 or episode_limit < 1 or T < 1 or world < 1:
+        raise ValueError("plan: E, episode_limit, T and world must be positive")
+    per_episode = world * E * episode_limit
     episodes = -(-int(g("steps_per_epoch")) // per_episode)
-    return Plan(int(g("steps_per_epoch")) * int(g("epochs")), max(int(g("update_after")), int(g("batch_size")) * T), T, per_episode,
-                episodes, episodes * per_episode, int(g("epochs")))
+    return Plan(int(g("steps_per_epoch")) * int(g("epochs")), max(int(g("update_after")), world * int(g("batch_size")) * T), T,
+                per_episode, episodes, episodes * per_episode, int(g("epochs")))
 
 
 def eps_thres(t: int, decay_steps: float) -> float:
@@ -105,12 +118,40 @@ def eps_thres(t: int, decay_steps: float) -> float:
     return max(EPS_END, -(EPS_START - EPS_END) / decay_steps * t + EPS_START)
 
 
-def derive_seeds(seed: int) -> Dict[str, int]:
+RANK_SEED_STRIDE = 4096
+RANK_SEEDS = ("train_env", "replay", "explore", "comm")            # what differs between the ranks of a data-parallel run
+
+
+def derive_seeds(seed: int, rank: int = 0) -> Dict[str, int]:
     """The seeds of a run's random states, all from ``seed``: torch's generator (parameter initialisation), the two simulators' placement
-    samplers, the replay's sampler, the exploration pair, the evaluation's pair, the DiscreteComm noise (+ the module's index)."""
+    samplers, the replay's sampler, the exploration pair, the evaluation's pair, the DiscreteComm noise (+ the module's index).  Rank r of
+    a data-parallel run shifts ``RANK_SEEDS`` by 4096 r: its own environments, ring samples, exploration and noise; ``torch`` is every
+    rank's (the parameters are rank 0's anyway), ``test_env`` and ``evaluation`` are read on rank 0 only."""
     base = 1000003 * int(seed)
-    return dict(torch=int(seed), train_env=base + 1, test_env=base + 2, replay=base + 3, explore=base + 4, evaluation=base + 5,
-                comm=base + 16)
+    seeds = dict(torch=int(seed), train_env=base + 1, test_env=base + 2, replay=base + 3, explore=base + 4, evaluation=base + 5,
+                 comm=base + 16)
+    return _rank_seeds(seeds, rank)
+
+
+def _rank_seeds(seeds: Dict[str, int], rank: int) -> Dict[str, int]:
+    if int(rank) < 0:
+        raise ValueError("rank must not be negative")
+    return {k: int(v) + (RANK_SEED_STRIDE * int(rank) if k in RANK_SEEDS else 0) for k, v in seeds.items()}
+
+
+def state_file(rank: int) -> str:
+    """The name of rank ``rank``'s state file in the run directory."""
+    return "state.pt" if int(rank) == 0 else f"state.rank{int(rank)}.pt"
+
+
+def _gather_ints(value: int, device, group):
+    """[value of every rank of ``group``], through one all-gather of an int64 on ``device``."""
+    import torch as th
+    import torch.distributed as dist
+    mine = th.tensor([int(value)], dtype=th.int64, device=device)
+    parts = [th.empty_like(mine) for _ in range(dist.get_world_size(group))]
+    dist.all_gather(parts, mine, group=group)
+    return [int(p) for p in parts]
 
 
 def comm_modules(learner):
@@ -268,10 +309,16 @@ class Run:
 
     Attributes a caller may read: ``learner``, ``env`` / ``test_env`` (the training and the evaluation simulator), ``replay``, ``stats``,
     ``film``, ``collect`` / ``train_episode`` (the collect-only and the training episode), ``evaluation``, ``plan``, ``seeds``, and the
-    host counters ``epoch`` (epochs finished), ``replays`` (episode replays finished), ``interacts``, ``elapsed``."""
+    host counters ``epoch`` (epochs finished), ``replays`` (episode replays finished), ``interacts``, ``elapsed``.
 
-    def __init__(self, ours: dict, args: SimpleNamespace, output_dir: str, exp_name: Optional[str], resuming: bool):
+    Data-parallel (``torch.distributed`` initialised when the run is built): ``world`` / ``rank`` / ``group``.  Every rank owns its
+    ``n_envs`` environments, its ring and its sampler (``seeds``: this rank's), the parameters are replicated and an update is
+    ``batch_size`` sequences per rank followed by one all-reduce.  ``test_env``, ``film``, ``evaluation`` and ``logger`` exist on rank 0
+    only (None elsewhere); ``interacts`` counts all ranks."""
+
+    def __init__(self, ours: dict, args: SimpleNamespace, output_dir: str, exp_name: Optional[str], resuming: bool, group=None):
         import torch as th
+        import torch.distributed as dist
 
         from .film import Film
         from .graphs import INFO_KEYS, Episode, Evaluation, GraphedEpisode, GraphedEvaluation
@@ -280,7 +327,19 @@ class Run:
         from .sim import BatchedSingleUbsCoverageEnv, BatchedUbsCoverageEnv
         from .stats import EpochStats
         self.ours, self.args, self.output_dir, self.exp_name = ours, args, output_dir, exp_name
-        exp, E, seeds = ours["exp"], int(ours["n_envs"]), ours["seeds"]
+        self.distributed = dist.is_available() and dist.is_initialized()
+        self.group = group if self.distributed else None
+        self.world, self.rank = (dist.get_world_size(group), dist.get_rank(group)) if self.distributed else (1, 0)
+        if self.rank < 0:
+            raise ValueError("this process is no member of `group`")
+        force = bool(ours.get("force_collective", False))
+        if force and not self.distributed:
+            raise ValueError("force_collective needs an initialised torch.distributed process group")
+        if int(ours.get("world", 1)) != self.world:
+            raise ValueError(f"the run is described for world size {ours.get('world', 1)}, the process group holds {self.world} ranks")
+        # the statistics merge, the replica check and the barrier of the state files run whenever the update holds its collective
+        self.collective = self.world > 1 or force
+        exp, E, seeds = ours["exp"], int(ours["n_envs"]), _rank_seeds(ours["seeds"], self.rank)      # config.json holds rank 0's
         self.exp, self.single, self.seeds, self.save_replay = exp, exp == "exp1", seeds, bool(ours["save_replay"])
         E_test = int(ours["n_test_envs"])
         if getattr(args, "mixer", False):
@@ -298,15 +357,16 @@ class Run:
             if args.o != enc:
                 raise ValueError(f"{exp} runs the {enc!r} observation encoder, args.o = {args.o!r}")
             make = lambda B, k: BatchedUbsCoverageEnv.from_map(spec, B, dev, seed=seeds[k])  # noqa: E731
-        self.enc, self.env, self.test_env = enc, make(E, "train_env"), make(E_test, "test_env")
+        self.enc, self.env, self.test_env = enc, make(E, "train_env"), make(E_test, "test_env") if self.rank == 0 else None
         env, test_env = self.env, self.test_env
-        th.manual_seed(seeds["torch"])           # parameter initialisation
-        self.learner = learner = (QLearner if self.single else MultiAgentQLearner)(env.get_env_info(enc), args)
-        if learner.needs_collective():
-            raise ValueError("a data-parallel run is not covered: the episode graphs hold the whole update (graphs.GraphedEpisode)")
+        th.manual_seed(seeds["torch"])           # parameter initialisation (data-parallel: rank 0's are broadcast)
+        self.learner = learner = (QLearner if self.single else MultiAgentQLearner)(env.get_env_info(enc), args, process_group=self.group)
+        if force:
+            learner.grads.force_collective = True        # before anything is captured: the episode graphs are cut at the all-reduce
+        assert learner.needs_collective() == self.collective
         seed_comm_modules(learner, seeds["comm"])
         T = int(args.max_seq_len) if args.max_seq_len else env.episode_limit
-        self.plan = plan(args, E, env.episode_limit, T)
+        self.plan = plan(args, E, env.episode_limit, T, self.world)
         if self.single:
             self.replay = SingleUbsSequenceReplay(int(args.replay_size), T, env.n_gts, args.hidden_size, n_envs=E, device=dev,
                                                   device_state=True, seed=seeds["replay"])
@@ -319,7 +379,7 @@ class Run:
         kw = dict(eps=(EPS_START, EPS_END, float(args.decay_steps)), updates_per_segment=int(ours["updates_per_segment"]), enc=enc)
         self.info_keys = tuple(k for k in INFO_KEYS if not (self.single and k == "ProbCollision"))
         self.stats = EpochStats(list(self.info_keys) + ["LossQ"] + ["Test" + k for k in self.info_keys], dev, cap=max(64, E, E_test))
-        self.film = Film(test_env, int(args.num_test_episodes))
+        self.film = Film(test_env, int(args.num_test_episodes)) if self.rank == 0 else None
         # the three captures run on the fresh, empty state - also when resuming: a warm-up episode commits into the ring at the restored
         # head, so captured after a full ring was loaded it would overwrite the oldest sequences.  `_load_state` copies IN PLACE afterwards
         self.collect = ep_cls(learner, env, self.replay, int(args.batch_size), train=False, stats=self.stats,
@@ -327,46 +387,63 @@ class Run:
         self.train_episode = ep_cls(learner, env, self.replay, int(args.batch_size), train=True, stats=self.stats,
                                     explore_seed=seeds["explore"], **kw)
         self.evaluation = ev_cls(learner, test_env, int(args.num_test_episodes), eps=TEST_EPS, seed=seeds["evaluation"], enc=enc,
-                                 stats=self.stats, film=self.film)
+                                 stats=self.stats, film=self.film) if self.rank == 0 else None
         self.epoch = self.replays = self.interacts = 0
         self.elapsed = 0.0
         self.active = "collect"          # the episode object whose `t` / `explore` are current
         self.ring_base = 0               # interactions when the ring was last empty: training starts update_after_eff later
-        self.logger = RunLogger(output_dir, exp_name, append=resuming)
+        self.logger = RunLogger(output_dir, exp_name, append=resuming) if self.rank == 0 else None
 
     # ---- construction -------------------------------------------------------------------------------------------------------------
     @classmethod
     def create(cls, exp: str, env, args, output_dir: str, exp_name: Optional[str] = None, seed: int = 0, n_envs: int = 32,
-               n_test_envs: Optional[int] = None, updates_per_segment: int = 1, graphed: bool = True, save_replay: bool = True) -> "Run":
+               n_test_envs: Optional[int] = None, updates_per_segment: int = 1, graphed: bool = True, save_replay: bool = True,
+               group=None, force_collective: bool = False) -> "Run":
         """Builds simulators, learner, replay, statistics, film and the three graphs (``graphed=False``: their eager forms) as
         run.py:47-61 builds them and writes ``config.json``; sets torch's generator (``torch.manual_seed(seed)``, as the reference's
         ``set_rand_seed`` does) for the parameter initialisation.  env: a map id of ``sim.MAPS`` or a ``MapSpec`` (exp2 / exp3), a
         ``SingleUbsParams`` (exp1).  n_test_envs: evaluation environments (default ``num_test_episodes``; must divide it).
         save_replay=False: ``state.pt`` leaves the ring out (gigabytes at exp3 sizes); a resumed run then collects ``update_after_eff``
-        interactions again before it trains and is NOT bit-identical to an uninterrupted one."""
+        interactions again before it trains and is NOT bit-identical to an uninterrupted one.
+
+        With ``torch.distributed`` initialised the run is data-parallel over ``group`` (default: the world) and EVERY rank calls
+        ``create`` with the same arguments but its own ``args.device``; ``n_envs`` and ``args.batch_size`` are per rank.
+        force_collective: the gradient all-reduce (and with it the cut episode graphs) also at world size 1."""
+        import torch.distributed as dist
         ns = check_args(exp, args)
+        world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         ours = dict(exp=exp, env=_env_to_config(exp, env), n_envs=int(n_envs),
                     n_test_envs=int(ns.num_test_episodes if n_test_envs is None else n_test_envs),
                     updates_per_segment=int(updates_per_segment), graphed=bool(graphed), save_replay=bool(save_replay),
-                    seeds=derive_seeds(seed))
-        run = cls(ours, ns, output_dir, exp_name, resuming=False)
-        env_fn, env_kwargs = _reference_env(exp, env)
-        config = dict(env_fn=env_fn, env_kwargs=env_kwargs, seed=int(seed), args=ns, uav_bs_ctrl_amd=ours)
-        run.logger.save_config(config)
-        for name in ("state.pt", "state.pt.tmp"):            # a new run in an old directory must not be resumable from the old state
-            if os.path.exists(os.path.join(output_dir, name)):
-                os.remove(os.path.join(output_dir, name))
+                    seeds=derive_seeds(seed), world=int(world), force_collective=bool(force_collective))
+        run = cls(ours, ns, output_dir, exp_name, resuming=False, group=group)
+        if run.rank == 0:
+            env_fn, env_kwargs = _reference_env(exp, env)
+            config = dict(env_fn=env_fn, env_kwargs=env_kwargs, seed=int(seed), args=ns, uav_bs_ctrl_amd=ours)
+            run.logger.save_config(config)
+            # a new run in an old directory must not be resumable from the old state: no rank writes a state file before the first
+            # epoch's collectives, which rank 0 enters after this
+            for name in os.listdir(output_dir):
+                if name.startswith("state.") and (name.endswith(".pt") or name.endswith(".pt.tmp")):
+                    os.remove(os.path.join(output_dir, name))
         return run
 
     @classmethod
-    def resume(cls, output_dir: str) -> "Run":
+    def resume(cls, output_dir: str, device=None, group=None) -> "Run":
         """Rebuilds the run of ``output_dir`` from ``config.json`` exactly as ``create`` built it - captures included, on the fresh
         state - then copies ``state.pt`` in place into the tensors the graphs hold addresses of, and re-opens ``progress.txt`` for
         append.  Raises ``RunDirectoryError`` for a directory without ``state.pt``, a ``config.json`` that does not rebuild the saved
-        shapes, and a run that is already complete."""
+        shapes, and a run that is already complete.
+
+        device: overrides ``args.device`` of ``config.json`` (a rank's own ``cuda:{LOCAL_RANK}``).  A data-parallel run is resumed by
+        every rank of a group of the saved world size, rank r from ``state.rank{r}.pt``; another world size, a rank file that is
+        missing and rank files of different epochs raise ``RunDirectoryError`` on EVERY rank, so none walks into a collective alone."""
         import torch as th
-        cfg_path, state_path = os.path.join(output_dir, "config.json"), os.path.join(output_dir, "state.pt")
-        if not os.path.exists(state_path):
+        import torch.distributed as dist
+        distributed = dist.is_available() and dist.is_initialized()
+        world, rank = (dist.get_world_size(group), dist.get_rank(group)) if distributed else (1, 0)
+        cfg_path, state_path = os.path.join(output_dir, "config.json"), os.path.join(output_dir, state_file(rank))
+        if not os.path.exists(os.path.join(output_dir, "state.pt")):
             raise RunDirectoryError(f"{output_dir}: no state.pt - nothing to resume (no epoch of this run was finished, or it is not a "
                                     f"run directory of this package)")
         try:
@@ -376,10 +453,26 @@ class Run:
             ns = check_args(ours["exp"], next(iter(config["args"].values())))
         except (OSError, KeyError, ValueError, StopIteration, AttributeError, TypeError) as e:
             raise RunDirectoryError(f"{output_dir}: config.json does not describe a run of this package ({type(e).__name__}: {e})") from e
+        if device is not None:
+            ns.device = str(device)
+        saved_world = int(ours.get("world", 1))
+        if saved_world != world:             # read from the same file on every rank: all of them raise
+            raise RunDirectoryError(f"{output_dir}: the run was saved at world size {saved_world}, this process group holds {world} "
+                                    f"rank{'s' if world != 1 else ''}")
+        if world > 1:
+            have = _gather_ints(os.path.exists(state_path), ns.device, group)
+            if not all(have):
+                missing = ", ".join(state_file(r) for r, h in enumerate(have) if not h)
+                raise RunDirectoryError(f"{output_dir}: a rank file is missing ({missing}): every rank of the saved run needs its own")
         state = th.load(state_path, map_location="cpu")
+        if world > 1:
+            epochs = _gather_ints(state["epoch"], ns.device, group)
+            if len(set(epochs)) != 1:
+                raise RunDirectoryError(f"{output_dir}: the rank files hold different epochs ({epochs} in rank order): the job was killed "
+                                        f"between their renames")
         if int(state["epoch"]) >= int(ns.epochs):
             raise RunDirectoryError(f"{output_dir}: the run is already complete ({state['epoch']} of {ns.epochs} epochs)")
-        run = cls(ours, ns, output_dir, config.get("exp_name"), resuming=True)
+        run = cls(ours, ns, output_dir, config.get("exp_name"), resuming=True, group=group)
         run._load_state(state)
         return run
 
@@ -389,15 +482,17 @@ class Run:
         lr, rb, opt = self.learner, self.replay, self.learner.optimizer
         out = {"learner.flat": lr.flat.flat, "learner.flat_target": lr.flat_target, "learner.m": opt.m, "learner.v": opt.v,
                "learner.hyper": opt.hyper, "replay.state": rb.state, "replay.rng": rb.rng, "replay.status": rb.status,
-               "env.rng": self.env.rng if self.single else self.env.map_rng,
-               "test_env.rng": self.test_env.rng if self.single else self.test_env.map_rng, "evaluation.rng": self.evaluation.rng}
+               "env.rng": self.env.rng if self.single else self.env.map_rng}
+        if self.rank == 0:                       # the evaluation is rank 0's alone
+            out.update({"test_env.rng": self.test_env.rng if self.single else self.test_env.map_rng, "evaluation.rng": self.evaluation.rng})
         for name, ep in (("collect", self.collect), ("train", self.train_episode)):
             out.update({f"{name}.t": ep.t, f"{name}.eps": ep.eps, f"{name}.explore": ep.explore})
         out.update({"comm." + name: m.rng_state for name, m in comm_modules(lr)})
         return out
 
     def _save_state(self) -> None:
-        """Written to a temporary name and renamed: a killed job leaves the previous state intact."""
+        """Written to a temporary name and renamed: a killed job leaves the previous state intact.  Data-parallel: every rank writes
+        its own file (``state_file``: its tensors, its ring), and renames it after a barrier that all temporary files precede."""
         import torch as th
         lr = self.learner
         state = dict(version=STATE_VERSION, epoch=self.epoch, replays=self.replays, interacts=self.interacts, elapsed=self.elapsed,
@@ -407,9 +502,12 @@ class Run:
         if self.save_replay:
             size = int(state["tensors"]["replay.state"][1])
             state["mem"] = {k: v[:size].cpu() for k, v in self.replay.mem.items()}
-        tmp = os.path.join(self.output_dir, "state.pt.tmp")
-        th.save(state, tmp)
-        os.replace(tmp, os.path.join(self.output_dir, "state.pt"))
+        path = os.path.join(self.output_dir, state_file(self.rank))
+        th.save(state, path + ".tmp")
+        if self.collective:
+            import torch.distributed as dist
+            dist.barrier(group=self.group)
+        os.replace(path + ".tmp", path)
 
     def _load_state(self, state: dict) -> None:
         lr, rb = self.learner, self.replay
@@ -422,7 +520,7 @@ class Run:
         if mem is not None:
             bad += [f"mem.{k}" for k in rb.mem if k not in mem or mem[k].shape[1:] != rb.mem[k].shape[1:] or mem[k].shape[0] > rb.capacity]
         if state.get("version") != STATE_VERSION or bad:
-            raise RunDirectoryError(f"{self.output_dir}: config.json does not rebuild the shapes state.pt holds (version "
+            raise RunDirectoryError(f"{self.output_dir}: config.json does not rebuild the shapes {state_file(self.rank)} holds (version "
                                     f"{state.get('version')}; {'; '.join(bad) or 'unknown layout'})")
         for k, v in live.items():
             v.copy_(saved[k])
@@ -466,37 +564,56 @@ class Run:
     def _end_epoch(self, k: int, start: float) -> None:
         """run.py:102-127 in its order: evaluation, lr_scheduler, checkpoint, films, checks, the row, then state.pt."""
         args, lr, log = self.args, self.learner, self.logger
-        self.evaluation()
+        first = self.rank == 0                           # data-parallel: rank 0 evaluates and writes, every rank checks and merges
+        if first:
+            self.evaluation()
         if lr.anneal_lr:
             lr.lr_scheduler.step()
         saving = k % int(args.save_freq) == 0
-        if saving or k == self.plan.epochs:
+        if first and (saving or k == self.plan.epochs):
             lr.save_checkpoint(os.path.join(self.output_dir, f"checkpoint_epoch{k}.pt"), stamp=dict(epoch=k, t=self.interacts - 1))
         host = None
-        if saving:
+        if first and saving:
             host = self.film.numpy()
             for n in range(self.film.episodes):
                 self.film.write(os.path.join(self.output_dir, f"epoch{k}_episode{n}"), n, host=host)
         self.replay.check()
-        self.film.check(host)
-        log.summary = row = self.stats.summary()         # the one device-to-host copy of the epoch's statistics
-        log.log_tabular("Epoch", k)
-        log.log_tabular("Episode", self.replays * self.env.B)
-        for key, mm, avg in ROW_KEYS[self.single]:
-            log.log_tabular(key, with_min_and_max=mm, average_only=avg)
-        log.log_tabular("TotalEnvInteracts", self.interacts)
-        log.log_tabular("LossQ", average_only=True)      # nan in an epoch without an update (the reference would raise there)
-        if self.single:
-            log.log_tabular("ExploreEps", eps_thres(self.interacts - 1, float(args.decay_steps)))
+        if first:
+            self.film.check(host)
+        if self.collective:
+            import torch.distributed as dist
+            self._check_replicas(k)
+            row = self.stats.summary(self.group or dist.group.WORLD)     # all ranks' values: one all-gather of the accumulators
+        else:
+            row = self.stats.summary()                   # the one device-to-host copy of the epoch's statistics
         self.elapsed = time.time() - start
-        log.log_tabular("Time", self.elapsed)
-        log.dump_tabular()
+        if first:
+            log.summary = row
+            log.log_tabular("Epoch", k)
+            log.log_tabular("Episode", self.replays * self.env.B * self.world)
+            for key, mm, avg in ROW_KEYS[self.single]:
+                log.log_tabular(key, with_min_and_max=mm, average_only=avg)
+            log.log_tabular("TotalEnvInteracts", self.interacts)
+            log.log_tabular("LossQ", average_only=True)  # nan in an epoch without an update (the reference would raise there)
+            if self.single:                              # the schedule counts a rank's OWN interactions (graphs.Episode: +E per step)
+                log.log_tabular("ExploreEps", eps_thres(self.interacts // self.world - 1, float(args.decay_steps)))
+            log.log_tabular("Time", self.elapsed)
+            log.dump_tabular()
         self.stats.reset()
         if row["NonFiniteLossQ"] > 0:
             raise TrainingDiverged(f"epoch {k}: {row['NonFiniteLossQ']} of {row['NonFiniteLossQ'] + row['NLossQ']} updates returned a "
                                    f"non-finite LossQ; the row was written, state.pt was not")
         self.epoch = k
         self._save_state()
+
+    def _check_replicas(self, k: int) -> None:
+        """An exact checksum of the flat parameter buffer (its bits as int32, summed in int64) from every rank: what bench.py reports
+        as ``replicas_identical``, enforced once per epoch."""
+        import torch as th
+        sums = _gather_ints(self.learner.flat.flat.view(th.int32).sum(dtype=th.int64), self.args.device, self.group)
+        if len(set(sums)) != 1:
+            raise ReplicasDiverged(f"epoch {k}: the ranks' parameters differ (checksums in rank order: {sums}); the row and the state "
+                                   f"files were not written")
 
 
 # ---- command line (run.py:181-195) ----------------------------------------------------------------------------------------------------
@@ -528,19 +645,50 @@ def main(argv=None) -> None:
     ap.add_argument("--eager", action="store_true", help="graphs.Episode / Evaluation instead of their graphs")
     ap.add_argument("--no-save-replay", action="store_true")
     ap.add_argument("--epochs", type=int, default=None, help="run this many more epochs, not all remaining ones")
+    ap.add_argument("--dist-backend", choices=("nccl", "gloo"), default="nccl", help="under a launcher that sets RANK: the backend of the group")
+    ap.add_argument("--dist-timeout", type=float, default=600.0, help="seconds after which a collective gives up on a missing rank")
+    ap.add_argument("--one-device", action="store_true", help="every rank stays on args.device instead of cuda:{LOCAL_RANK}")
     a = ap.parse_args(argv)
-    if a.resume:
-        run = Run.resume(a.out)
-    else:
-        if not (a.exp and a.env and a.args_json):
-            ap.error("--exp, --env and --args-json are required without --resume")
-        with open(a.args_json) as f:
-            args = json.load(f)
-        run = Run.create(a.exp, _parse_env(a.exp, a.env), args, a.out, exp_name=a.exp_name or a.exp, seed=a.seed, n_envs=a.envs,
-                         n_test_envs=a.test_envs, updates_per_segment=a.updates_per_segment, graphed=not a.eager,
-                         save_replay=not a.no_save_replay)
-    run.train(a.epochs)
-    print(f"{a.out}: epoch {run.epoch} of {run.plan.epochs}, {run.interacts} interactions, {run.elapsed:.1f} s")
+    if not a.resume and not (a.exp and a.env and a.args_json):
+        ap.error("--exp, --env and --args-json are required without --resume")
+    device = _init_distributed(a) if "RANK" in os.environ else None
+    try:
+        if a.resume:
+            run = Run.resume(a.out, device=device)
+        else:
+            with open(a.args_json) as f:
+                args = json.load(f)
+            if device is not None:
+                args["device"] = device
+            run = Run.create(a.exp, _parse_env(a.exp, a.env), args, a.out, exp_name=a.exp_name or a.exp, seed=a.seed, n_envs=a.envs,
+                             n_test_envs=a.test_envs, updates_per_segment=a.updates_per_segment, graphed=not a.eager,
+                             save_replay=not a.no_save_replay)
+        run.train(a.epochs)
+        if run.rank == 0:
+            print(f"{a.out}: epoch {run.epoch} of {run.plan.epochs}, {run.interacts} interactions, {run.elapsed:.1f} s")
+    finally:
+        if "RANK" in os.environ:
+            import torch.distributed as dist
+            if dist.is_initialized():
+                dist.destroy_process_group()
+
+
+def _init_distributed(a) -> Optional[str]:
+    """A process started by ``python -m torch.distributed.run`` (RANK in its environment) initialises the group itself; returns the
+    device of this rank, ``cuda:{LOCAL_RANK}``, or None with ``--one-device`` (every rank on ``args.device``: world-size-2 tests on one
+    GPU over gloo)."""
+    import datetime
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # RCCL across processes: dmabuf IPC, set before the first HIP call
+    import torch as th
+    import torch.distributed as dist
+    device = None if a.one_device else f"cuda:{int(os.environ.get('LOCAL_RANK', 0))}"
+    if device is not None:
+        th.cuda.set_device(device)
+    kw = dict(timeout=datetime.timedelta(seconds=a.dist_timeout))
+    if a.dist_backend == "nccl" and device is not None:
+        kw["device_id"] = th.device(device)
+    dist.init_process_group(a.dist_backend, **kw)
+    return device
 
 
 if __name__ == "__main__":

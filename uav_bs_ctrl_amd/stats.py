@@ -5,6 +5,7 @@ one launch per push and read with ONE device-to-host copy when the row is printe
     st = EpochStats(["EpRet", "EpLen", "LossQ", "TestEpRet"], "cuda")
     st.push(EpRet=info["EpRet"], EpLen=info["EpLen"])         # any subset of the keys, equal element counts; no host synchronisation
     row = st.summary()                                        # {AverageEpRet, StdEpRet, MaxEpRet, MinEpRet, NEpRet, NonFiniteEpRet, ...}
+    row = st.summary(group)                                   # data-parallel: of ALL ranks' values (one all-gather + ``merge_acc``)
     st.reset()
 
 ``push`` copies every tensor into its row of a fixed float64 staging buffer (``copy_`` casts int32 / float32 and reads strided views such
@@ -14,7 +15,7 @@ only (earlier buffers stay alive: a graph captured before the growth keeps pushi
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import torch as th
 
@@ -22,6 +23,33 @@ from . import _lib as L
 
 MAX_KEYS_PER_LAUNCH = 16
 EMPTY = (0.0, 0.0, 0.0, math.inf, -math.inf, 0.0)       # {count, mean, M2, min, max, non-finite count}
+
+
+def merge_acc(accs) -> List[List[float]]:
+    """The accumulator of all values a list of accumulators saw: ``accs`` holds [K, 6] tables {count, mean, M2, min, max, non-finite count}
+    (nested lists, arrays or tensors) and the result is their merge IN LIST ORDER by the pairwise update of uavgnn_stats_push (Chan et
+    al.), as nested lists of Python floats - float64 on the host, no launch.  Counts and non-finite counts add, min and max combine; an
+    empty accumulator (count 0) is the identity, so the merge of one table is that table, bit for bit."""
+    tables = [a.tolist() if hasattr(a, "tolist") else [list(r) for r in a] for a in accs]
+    if not tables:
+        raise ValueError("merge_acc: an empty list of accumulators")
+    if any(len(t) != len(tables[0]) or any(len(r) != 6 for r in t) for t in tables):
+        raise ValueError("merge_acc: accumulators of shape [K, 6] with equal K expected")
+    out = []
+    for rows in zip(*tables):
+        count, mean, m2, lo, hi, bad = (float(v) for v in EMPTY)
+        for n_b, mean_b, m2_b, lo_b, hi_b, bad_b in rows:
+            bad += float(bad_b)
+            if not n_b > 0:
+                continue
+            if count > 0:
+                d, n2 = float(mean_b) - mean, count + float(n_b)
+                mean, m2 = mean + d * float(n_b) / n2, m2 + (float(m2_b) + d * d * count * float(n_b) / n2)
+                count, lo, hi = n2, min(lo, float(lo_b)), max(hi, float(hi_b))
+            else:
+                count, mean, m2, lo, hi = float(n_b), float(mean_b), float(m2_b), float(lo_b), float(hi_b)
+        out.append([count, mean, m2, lo, hi, bad])
+    return out
 
 
 class EpochStats:
@@ -82,8 +110,16 @@ class EpochStats:
         """What a graph capture snapshots before its warm-up and restores after the capture."""
         return [self.acc]
 
-    def summary(self) -> Dict[str, float]:
-        acc = self.acc.cpu().tolist()            # the one device-to-host copy
+    def summary(self, group=None) -> Dict[str, float]:
+        """group: a ``torch.distributed`` process group - the accumulators of all its ranks are all-gathered (ONE collective of
+        K x 6 doubles) and every rank returns the summary of their merge in rank order (``merge_acc``).  None: this process's alone."""
+        if group is None:
+            acc = self.acc.cpu().tolist()        # the one device-to-host copy
+        else:
+            import torch.distributed as dist
+            parts = [th.empty_like(self.acc) for _ in range(dist.get_world_size(group))]
+            dist.all_gather(parts, self.acc, group=group)
+            acc = merge_acc(th.stack(parts).cpu().tolist())
         out: Dict[str, float] = {}
         for k, (count, mean, m2, lo, hi, bad) in zip(self.keys, acc):
             out["Average" + k] = mean if count > 0 else math.nan
