@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define UAVGNN_VERSION 100 /* 0.1.0 */
+#define UAVGNN_VERSION 101 /* 0.1.1 */
 
 #define UAVGNN_EINVAL (-1000)      /* null pointer / non-positive size */
 #define UAVGNN_EUNSUPPORTED (-1001) /* shape outside the compiled instantiations */
@@ -437,19 +437,18 @@ int uavgnn_talk_attn_env_bwd(const float* s, int ld_s, const float* q, int ld_q,
  *                                (uavgnn_tarmac_msg_weight_bytes(H, M, K) bytes, 16-byte aligned); once per weight version;
  *   uavgnn_tarmac_msg_fwd        c_out [N, M] (row stride ld_c) always; training outputs, each optional (NULL): a_save [E]
  *                                attention weight per CSC position, proj_out [N, M + 2K], x_copy [N, H] (the x half of the GRU
- *                                input [x || c]); planes_out (NULL or uavgnn_tarmac_msg_planes_bytes(N, H, M) bytes): the GEMM
- *                                operand [x || c || h] of uavgnn_gru_cell_fwd_planes as bf16 planes in that kernel's tile order.
+ *                                input [x || c]).  M + 2K <= 96 runs the wavefront-pair kernel, wider projections the
+ *                                one-wavefront-per-row-tile kernel.
  * Preconditions: every graph has exactly n_ag agents (rows i n_ag .. (i + 1) n_ag - 1; N % n_ag == 0; 16 % n_ag == 0: no graph
  * straddles two 16-row tiles, the unit a wavefront works on); the rows of a tile have at most 256 in-edges, all from rows of the
  * same tile - a violating tile gets NaN messages, never a silent fallback. */
 int uavgnn_tarmac_msg_supported(int H, int M, int K, int n_ag);
 long long uavgnn_tarmac_msg_weight_bytes(int H, int M, int K);
-long long uavgnn_tarmac_msg_planes_bytes(int N, int H, int M);
 int uavgnn_tarmac_msg_prepare(const float* Wp, int ld, int H, int M, int K, void* tiles, uavgnn_stream_t stream);
 int uavgnn_tarmac_msg_fwd(const float* x, int ld_x, const float* h, int ld_h, int N, int H, int n_ag, const void* tiles,
                           const float* bias, int M, int K, const int32_t* talk_off, const int32_t* talk_src, float scale,
                           float* c_out, int ld_c, float* a_save, float* proj_out, int ld_p, float* x_copy, int ld_xc,
-                          void* planes_out, uavgnn_stream_t stream);
+                          uavgnn_stream_t stream);
 /* ... that also writes row_absmax [N] = max(|x_row|, |c_row|, |h_row|) per agent - the row scales of uavgnn_gru_cell_fwd_h2 behind it
  * (every element of x and h passes through this kernel anyway; a maximum is order-independent: deterministic).  Wavefront-pair
  * kernel only: M + 2K <= 96 (uavgnn_tarmac_msg_rowmax_supported), UAVGNN_EUNSUPPORTED otherwise. */

@@ -100,9 +100,9 @@ for rnd in (1, 2):
     co, rmo = th.empty(N, M, device=dev), th.empty(N, device=dev)
     a_s, proj, xc = th.empty(N * n, device=dev), th.empty(N, M + 2 * K, device=dev), th.empty(N, K_in, device=dev)
     head = (x.data_ptr(), H, h.data_ptr(), H, N, H, n, tiles.data_ptr(), bp.data_ptr(), M, K, off.data_ptr(), src.data_ptr(), 1.0 / K)
-    t_a = time_us(lambda: L.check(lib.uavgnn_tarmac_msg_fwd(*head, co.data_ptr(), M, None, None, 0, None, 0, None, st), "msg"))
+    t_a = time_us(lambda: L.check(lib.uavgnn_tarmac_msg_fwd(*head, co.data_ptr(), M, None, None, 0, None, 0, st), "msg"))
     t_b = time_us(lambda: L.check(lib.uavgnn_tarmac_msg_fwd_rowmax(*head, co.data_ptr(), M, None, None, 0, None, 0, rmo.data_ptr(), st), "msg rm"))
-    t_c = time_us(lambda: L.check(lib.uavgnn_tarmac_msg_fwd(*head, xc.data_ptr() + 4 * H, K_in, a_s.data_ptr(), proj.data_ptr(), M + 2 * K, xc.data_ptr(), K_in, None, st), "msg tr"))
+    t_c = time_us(lambda: L.check(lib.uavgnn_tarmac_msg_fwd(*head, xc.data_ptr() + 4 * H, K_in, a_s.data_ptr(), proj.data_ptr(), M + 2 * K, xc.data_ptr(), K_in, st), "msg tr"))
     t_d = time_us(lambda: L.check(lib.uavgnn_tarmac_msg_fwd_rowmax(*head, xc.data_ptr() + 4 * H, K_in, a_s.data_ptr(), proj.data_ptr(), M + 2 * K, xc.data_ptr(), K_in, rmo.data_ptr(), st), "msg tr rm"))
     want = th.maximum(th.maximum(x.abs().max(1).values, h.abs().max(1).values), xc[:, H:].abs().max(1).values)
     print(f"tarmac_msg_fwd: no-grad {t_a:5.1f} us, + row maxima {t_b:5.1f} us | training {t_c:5.1f} us, + row maxima {t_d:5.1f} us | row maxima exact: {bool(th.equal(rmo, want))}")

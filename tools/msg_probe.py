@@ -1,5 +1,6 @@
 """Times the fused TarMAC message launch (csrc/tarmac_msg.hip) at C3 size against what it replaces (two projection GEMMs +
-uavgnn_talk_attn_env_fwd), per call class.  usage: python tools/msg_probe.py [B n]"""
+uavgnn_talk_attn_env_fwd), per call class.  usage: python tools/msg_probe.py [B n [M K]]
+M + 2K <= 96 (the default, 64 and 16) times the wavefront-pair kernel, wider projections (100 14) the one-wavefront kernel."""
 import sys
 
 import torch as th
@@ -10,7 +11,8 @@ import bench  # noqa: E402
 from uav_bs_ctrl_amd import _lib as L, ops  # noqa: E402
 
 B, n = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (4096, 8)
-H, M, K = 256, 64, 16
+M, K = (int(sys.argv[3]), int(sys.argv[4])) if len(sys.argv) > 4 else (64, 16)
+H = 256
 dev = th.device("cuda")
 gen = th.Generator(device=dev)
 gen.manual_seed(0)
@@ -27,7 +29,6 @@ c = th.empty(N, M, device=dev)
 inp = th.empty(N, H + M, device=dev)
 a_save = th.empty(E, device=dev)
 proj = th.empty(N, M + 2 * K, device=dev)
-planes = th.empty(lib.uavgnn_tarmac_msg_planes_bytes(N, H, M), dtype=th.uint8, device=dev)
 
 
 def timeit(fn, reps=30):
@@ -43,12 +44,12 @@ def timeit(fn, reps=30):
     return 1e3 * e0.elapsed_time(e1) / reps
 
 
-def msg(train, pl, dbg=0):
+def msg(train):
     def f():
-        rc = lib.uavgnn_tarmac_msg_fwd_dbg(x.data_ptr(), H, h.data_ptr(), H, N, H, n, tiles.data_ptr(), bp.data_ptr(), M, K, off.data_ptr(),
-                                           src.data_ptr(), 1.0 / K, (inp.data_ptr() + 4 * H) if train else c.data_ptr(), (H + M) if train else M,
-                                           a_save.data_ptr() if train else None, proj.data_ptr() if train else None, M + 2 * K,
-                                           inp.data_ptr() if train else None, H + M, planes.data_ptr() if pl else None, dbg, L.stream())
+        rc = lib.uavgnn_tarmac_msg_fwd(x.data_ptr(), H, h.data_ptr(), H, N, H, n, tiles.data_ptr(), bp.data_ptr(), M, K, off.data_ptr(),
+                                       src.data_ptr(), 1.0 / K, (inp.data_ptr() + 4 * H) if train else c.data_ptr(), (H + M) if train else M,
+                                       a_save.data_ptr() if train else None, proj.data_ptr() if train else None, M + 2 * K,
+                                       inp.data_ptr() if train else None, H + M, L.stream())
         assert rc == 0
     return f
 
@@ -76,25 +77,16 @@ off_none = th.zeros_like(off)
 
 def msg_noedges():
     rc = lib.uavgnn_tarmac_msg_fwd(x.data_ptr(), H, h.data_ptr(), H, N, H, n, tiles.data_ptr(), bp.data_ptr(), M, K, off_none.data_ptr(),
-                                   src.data_ptr(), 1.0 / K, c.data_ptr(), M, None, None, 0, None, 0, None, L.stream())
+                                   src.data_ptr(), 1.0 / K, c.data_ptr(), M, None, None, 0, None, 0, L.stream())
     assert rc == 0
 
 
+kernel = "wavefront pair per row tile" if M + 2 * K <= 96 else "one wavefront per row tile"
+print(f"# N = {N} rows ({B} graphs of {n}), H {H}, M {M}, K {K}: {kernel}; us per call, 30 back-to-back calls between one event pair")
 print(f"# fused launch on a batch WITHOUT talk edges (GEMM loop + outputs only): {timeit(msg_noedges):.1f} us")
-for dbg, what in ((1, "no weight-slice traffic"), (2, "no MFMAs"), (4, "no activation loads"), (8, "no barriers"), (3, "no weights, no MFMAs"),
-                  (7, "no weights / MFMAs / activation loads"), (15, "nothing but the split and the tail")):
-    def f(dbg=dbg):
-        assert lib.uavgnn_tarmac_msg_fwd_dbg(x.data_ptr(), H, h.data_ptr(), H, N, H, n, tiles.data_ptr(), bp.data_ptr(), M, K, off_none.data_ptr(),
-                                             src.data_ptr(), 1.0 / K, c.data_ptr(), M, None, None, 0, None, 0, None, dbg, L.stream()) == 0
-    print(f"#   ablation (no edges, one wavefront per row tile) dbg={dbg:2d} {what:42s}: {timeit(f):6.1f} us")
-print(f"# N = {N} rows ({B} graphs of {n}), H {H}, M {M}, K {K}; us per call, 30 back-to-back calls between one event pair")
 for train in (False, True):
     t_old = timeit(old(train))
-    t_new = timeit(msg(train, False))
-    t_one = timeit(msg(train, False, 16))
-    t_pl = timeit(msg(train, True))
+    t_new = timeit(msg(train))
     rd = 2 * N * H * 4
     wr = N * M * 4 + (N * (H + M + 2 * K) * 4 + E * 4 if train else 0)
-    print(f"train={int(train)}: two GEMMs + K3b {t_old:7.1f} | fused, wavefront pair per row tile {t_new:7.1f} ({(rd + wr) / t_new / 1e6:.2f} TB/s algorithmic) | "
-          f"one wavefront per row tile {t_one:7.1f} | "
-          f"fused + operand planes {t_pl:7.1f} ({(rd + wr + planes.numel()) / t_pl / 1e6:.2f} TB/s)")
+    print(f"train={int(train)}: two GEMMs + K3b {t_old:7.1f} | fused {t_new:7.1f} ({(rd + wr) / t_new / 1e6:.2f} TB/s algorithmic)")

@@ -1,4 +1,4 @@
-// Fast gate non-linearities of the matrix-core GRU cells (csrc/gru_x3.hip, csrc/gru_x3p.hip, csrc/gru_h2.hip).
+// Fast gate non-linearities of the matrix-core GRU cells (csrc/gru_x3.hip, csrc/gru_h2.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,4 +1,4 @@
-// K3a + K3b in ONE launch: the TarMAC message of /root/reference/algos/madrqn/agents/gnn_agents.py:254-267
+// K3a + K3b in ONE launch: the TarMAC message of the reference's algos/madrqn/agents/gnn_agents.py:254-267
 //   proj = [x || stopgrad(h)] Wp^T + bp            (f_val | f_sign | f_que stacked: value M | signature K | query K columns)
 //   c_v  = sum_{u -> v} softmax_u(<s_u, q_v> / K) val_u        over the `talk` relation
 // for batches of SMALL graphs with a uniform number of agents (dgl.batch of per-environment graphs, common.py:45,
@@ -22,15 +22,17 @@
 // attention weights per CSC position (training), proj (training: what talk_attn_env_bwd and the projection weight gradients
 // read), the x half of [x || c] (training; the rows are in registers anyway).
 //
-// PLANES (optional, `planes_out`): the same launch hands the GRU cell its GEMM operands [x || c || h] as bf16 planes in the
-// tile order the cell's loader copies verbatim - the exact three-way split of every activation is made ONCE here, in a
-// bandwidth-bound kernel whose VALU is idle, instead of by each of the four column-block workgroups of the cell
-// (csrc/gru_x3.hip spends ~70 VALU + 35 LDS stores per 36 MFMAs on it: DESIGN.md section 5).
+//
+// Two kernels, chosen by the projection width alone (msg_launch):
+//   * M + 2K <= 96 (four or six column tiles): tarmac_msg_fwd_k2_kernel - a row tile belongs to a PAIR of wavefronts that split
+//     the contraction (x half | h half); it can also write the row maxima the f16x2 GRU cell scales by.  Every shipped
+//     configuration runs here;
+//   * M + 2K = 97 .. 128 (seven or eight column tiles): tarmac_msg_fwd_kernel - the layout above, one wavefront per row tile,
+//     eight column tiles (the pair kernel's weight stages would take 96 KB of LDS there: one workgroup per CU).  No row maxima.
 #include <math.h>
 
 #include "bf16x3.h"
 #include "common.h"
-#include "uavgnn_probe.h"
 
 namespace uavgnn {
 namespace {
@@ -47,7 +49,7 @@ __device__ __forceinline__ bf16x8 frag_of(unsigned a, unsigned b, unsigned c, un
 }
 
 // workgroup barrier that orders LDS traffic only (s_waitcnt lgkmcnt(0) + s_barrier): __syncthreads() also drains the global stores
-// in flight (s_waitcnt vmcnt(0)) - the plane / x-copy stores of a K slice would be waited for at every slice
+// in flight (s_waitcnt vmcnt(0)) - the x-copy stores of a K slice would be waited for at every slice
 __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
   __builtin_amdgcn_s_barrier();
@@ -110,25 +112,26 @@ __device__ __forceinline__ void msg_scatter(float* __restrict__ Mx, int nmax, co
   }
 }
 
-// CT: column tiles of 16 (M + 2K <= 16 CT).  TRAIN: proj / attention weights / x copy are written.  PLANES: the [x || c || h]
-// operand planes of the GRU cell are written.
+// One wavefront per row tile, for M + 2K = 97 .. 128: eight column tiles of 16 (the weight tiles are padded to 128 rows).  TRAIN:
+// proj / attention weights / x copy are written.
 // The attention treats the 16 rows of a wavefront as ONE graph of 16 nodes (its 16 / n whole graphs side by side: a block-diagonal
 // dense A[16 x 16]): one pass of the edge / softmax / scatter / A V sequence per wavefront instead of one per graph - that
 // sequence is a chain of LDS round trips whose latency, not its work, is what a wavefront pays.
-template <int CT, bool TRAIN, bool PLANES>
-__global__ __launch_bounds__(kMsgThreads, CT == 8 ? 2 : 3) void tarmac_msg_fwd_kernel(
+template <bool TRAIN>
+__global__ __launch_bounds__(kMsgThreads, 2) void tarmac_msg_fwd_kernel(
     const float* __restrict__ x, int ld_x, const float* __restrict__ h, int ld_h, int N, int H, int n_ag,
     const u32x4* __restrict__ Wt, const float* __restrict__ bias, int M, int K, const int32_t* __restrict__ talk_off,
     const int32_t* __restrict__ talk_src, float scale, float* __restrict__ c_out, int ld_c, float* __restrict__ a_save,
-    float* __restrict__ proj_out, int ld_p, float* __restrict__ x_copy, int ld_xc, u32x4* __restrict__ planes_out, int dbg) {
+    float* __restrict__ proj_out, int ld_p, float* __restrict__ x_copy, int ld_xc) {
+  constexpr int CT = 8;                             // column tiles of 16
   constexpr int RP = 16 * CT;                       // padded projection columns
   constexpr int BCH = 3 * RP * 4;                   // 16-byte chunks of one weight slice (3 planes)
   constexpr int BPT = (BCH + kMsgThreads - 1) / kMsgThreads;
   constexpr int LDP = RP + 1;                       // odd row stride of the projection tile
   constexpr int NA = 16, EMAX = NA * NA;
   constexpr int kScratch = (NA + 4) + 5 * EMAX;     // OFF (padded to 20 words: SC .. AV stay 16-byte aligned) | SC | AD | SRC | DST | AV
-  // ONE LDS region, two lives: the double-buffered weight slices while the GEMM loop runs, then (behind the loop's last barrier)
-  // the projection tiles + the attention scratch of the four wavefronts - 45 KB at M + 2K = 96: three workgroups per CU
+  // ONE LDS region, two lives: the double-buffered weight slices while the GEMM loop runs (48 KB), then (behind the loop's last
+  // barrier) the projection tiles + the attention scratch of the four wavefronts (53 KB): two workgroups per CU
   constexpr int kLoopBytes = 2 * BCH * 16, kTailBytes = kMsgWaves * (16 * LDP + kScratch) * 4;
   __shared__ __attribute__((aligned(16))) unsigned char smem_raw[kLoopBytes > kTailBytes ? kLoopBytes : kTailBytes];
   u32x4(*sB)[BCH] = reinterpret_cast<u32x4(*)[BCH]>(smem_raw);
@@ -161,27 +164,9 @@ __global__ __launch_bounds__(kMsgThreads, CT == 8 ? 2 : 3) void tarmac_msg_fwd_k
 #pragma unroll
     for (int i = 0; i < BPT; ++i) sB[buf][min(tid + kMsgThreads * i, BCH - 1)] = rb[i];   // clamped duplicates: same data, same address
   };
-  // plane tile of the GRU cell: [row block of 128][slice][plane][128 rows][4 chunks], chunk q of row r (k = 8q .. 8q+7) at r * 4 +
-  // (q ^ swz32(r)).  A lane holds two 4-k pieces of a slice: k 4g.. -> chunk g >> 1, half g & 1;  k 16+4g.. -> chunk 2 + (g >> 1)
-  const int nsl_cell = nsx + (M + 31) / 32 + nsx;               // slices of [x || c || h]
-  const int r128 = row & 127;
-  u32x2* const pl_base = PLANES ? reinterpret_cast<u32x2*>(planes_out + (static_cast<size_t>(row >> 7) * nsl_cell * 3) * 512 + r128 * 4) +
-                                      (g & 1)
-                                : nullptr;
-  const int pl_q0 = 2 * ((g >> 1) ^ swz32(r128)), pl_q1 = 2 * ((2 + (g >> 1)) ^ swz32(r128));
-  auto store_planes = [&](int cell_slice, const Planes8& pl) {
-    if (PLANES && row < N) {
-#pragma unroll
-      for (int p = 0; p < 3; ++p) {
-        u32x2* d = pl_base + (static_cast<size_t>(cell_slice) * 3 + p) * 1024;
-        d[pl_q0] = u32x2{pl.p[p][0], pl.p[p][1]};
-        d[pl_q1] = u32x2{pl.p[p][2], pl.p[p][3]};
-      }
-    }
-  };
 
   // activations FOUR slices ahead in a ring of named registers (the x / h rows stream from HBM: what hides their latency is
-  // bytes in flight - 3 workgroups x 4 wavefronts x 4 slices x 2 KB = 96 KB per CU)
+  // bytes in flight - 2 workgroups x 4 wavefronts x 4 slices x 2 KB = 64 KB per CU)
   float4 a0_lo, a0_hi, a1_lo, a1_hi, a2_lo, a2_hi, a3_lo, a3_hi;
 #define UAVGNN_MSG_LOAD_A(LO, HI, S)                          \
   {                                                           \
@@ -218,8 +203,8 @@ __global__ __launch_bounds__(kMsgThreads, CT == 8 ? 2 : 3) void tarmac_msg_fwd_k
 #define UAVGNN_MSG_TERM(FA, PB)                                                                                      \
   acc[cp] = mfma(FA, as_frag(sb[(PB) * RP * 4 + (cp * 16 + j) * 4 + (g ^ swz(j))]), acc[cp]);                        \
   acc[cp + 1] = mfma(FA, as_frag(sb[(PB) * RP * 4 + ((cp + 1) * 16 + j) * 4 + (g ^ swz(j))]), acc[cp + 1]);
-  // one K slice: split the ring entry, (training) its x copy / (planes) its split planes, 6 CT MFMAs against the weight slice in
-  // LDS, reload the entry four slices ahead, move the next weight slice into the other buffer
+  // one K slice: split the ring entry, (training) its x copy, 6 CT MFMAs against the weight slice in LDS, reload the entry four
+  // slices ahead, move the next weight slice into the other buffer
 #define UAVGNN_MSG_STEP(LO, HI, T)                                                                   \
   if ((T) < ns) {                                                                                    \
     const int t_ = (T);                                                                              \
@@ -229,21 +214,16 @@ __global__ __launch_bounds__(kMsgThreads, CT == 8 ? 2 : 3) void tarmac_msg_fwd_k
       *reinterpret_cast<float4*>(d) = LO;                                                            \
       *reinterpret_cast<float4*>(d + 16) = HI;                                                       \
     }                                                                                                \
-    store_planes(t_ < nsx ? t_ : t_ - nsx + nsl_cell - nsx, pa);                                     \
-    if (!(dbg & 4)) UAVGNN_MSG_LOAD_A(LO, HI, t_ + 4)                                                \
+    UAVGNN_MSG_LOAD_A(LO, HI, t_ + 4)                                                                \
     const bf16x8 fa0 = as_frag(pa.p[0]), fa1 = as_frag(pa.p[1]), fa2 = as_frag(pa.p[2]);            \
     const u32x4* sb = sB[t_ & 1];                                                                    \
-    if (!(dbg & 2)) {                                                                                \
-      _Pragma("unroll") for (int cp = 0; cp < CT; cp += 2) {                                         \
-        UAVGNN_MSG_TERM(fa0, 2) UAVGNN_MSG_TERM(fa2, 0) UAVGNN_MSG_TERM(fa1, 1) UAVGNN_MSG_TERM(fa0, 1) \
-        UAVGNN_MSG_TERM(fa1, 0) UAVGNN_MSG_TERM(fa0, 0)                                              \
-      }                                                                                              \
+    _Pragma("unroll") for (int cp = 0; cp < CT; cp += 2) {                                           \
+      UAVGNN_MSG_TERM(fa0, 2) UAVGNN_MSG_TERM(fa2, 0) UAVGNN_MSG_TERM(fa1, 1) UAVGNN_MSG_TERM(fa0, 1) \
+      UAVGNN_MSG_TERM(fa1, 0) UAVGNN_MSG_TERM(fa0, 0)                                                \
     }                                                                                                \
-    if (!(dbg & 1)) {                                                                                \
-      store_b((t_ + 1) & 1);   /* its readers passed the barrier of iteration t - 1 */               \
-      load_b(t_ + 2);                                                                                \
-    }                                                                                                \
-    if (!(dbg & 8)) lds_barrier();                                                                   \
+    store_b((t_ + 1) & 1);   /* its readers passed the barrier of iteration t - 1 */                 \
+    load_b(t_ + 2);                                                                                  \
+    lds_barrier();                                                                                   \
   }
   for (int t = 0; t < ns; t += 4) {
     UAVGNN_MSG_STEP(a0_lo, a0_hi, t)
@@ -358,31 +338,19 @@ __global__ __launch_bounds__(kMsgThreads, CT == 8 ? 2 : 3) void tarmac_msg_fwd_k
     }
   }
   wave_sync_lds();
-  // ---- c: rows to memory, and (PLANES) its split planes as slices nsx .. of the cell operand --------------------------
+  // ---- c: rows to memory ----------------------------------------------------------------------------------------------
   for (int r = 0; r < 16; ++r) {
     if (row0 + r >= N) break;
     float* d = c_out + static_cast<size_t>(row0 + r) * ld_c;
     for (int ch = lane; ch < M; ch += kWave) d[ch] = P[r * LDP + ch];
   }
-  if (PLANES) {
-    for (int cs = 0; cs * 32 < M; ++cs) {
-      float v[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int ch = 32 * cs + 4 * g + (i & 3) + 16 * (i >> 2);
-        v[i] = ch < M ? P[j * LDP + ch] : 0.f;
-      }
-      store_planes(nsx + cs, split8(float4{v[0], v[1], v[2], v[3]}, float4{v[4], v[5], v[6], v[7]}));
-    }
-  }
 }
-
 
 // ---- two wavefronts per row tile (split K) ------------------------------------------------------------------------------------
 // N / 16 row tiles are two wavefronts per SIMD at C3, each walking a serial chain of 16 slices (load - split - 36 MFMAs - barrier)
-// and then the attention: the parts of tools/msg_probe.py's ablation ADD (11 us split + tail, 8 us activation stream, 11.6 us
-// weights + MFMAs = 31.5 us).  Here a row tile belongs to a PAIR of wavefronts of one workgroup (eight wavefronts, 64 rows): wave
-// `tile` contracts the x half of [x || h] (+ bias), wave `4 + tile` the h half - half the chain each, four wavefronts per SIMD to
+// and then the attention: the parts of that chain, timed with the others switched off ("Where the 34 us go"), ADD (11 us
+// split + tail, 8 us activation stream, 11.6 us weights + MFMAs = 31.5 us).  Here a row tile belongs to a PAIR of wavefronts of one
+// workgroup (eight wavefronts, 64 rows): wave `tile` contracts the x half of [x || h] (+ bias), wave `4 + tile` the h half - half the chain each, four wavefronts per SIMD to
 // hide each other's waits; a weight stage in LDS holds the x slice t AND the h slice t.  The h partial is added to the tile in
 // LDS, then the first wavefront of the pair runs the attention while the second writes `proj` (training).  The sum is
 // (x part + bias) + h part - the order of the two-GEMM path of rounds 1-4 -, not the single 16-slice chain of the kernel above.
@@ -659,13 +627,6 @@ extern "C" long long uavgnn_tarmac_msg_weight_bytes(int H, int M, int K) {
   return static_cast<long long>(2 * H / 32) * 3 * msg_rows_padded(M, K) * 64;
 }
 
-// bytes of the [x || c || h] operand planes for N rows (whole 128-row blocks)
-extern "C" long long uavgnn_tarmac_msg_planes_bytes(int N, int H, int M) {
-  if (N <= 0 || H <= 0 || M <= 0) return 0;
-  const long long nsl = 2 * (H / 32) + (M + 31) / 32;
-  return ((static_cast<long long>(N) + 127) / 128) * nsl * 3 * 8192;
-}
-
 extern "C" int uavgnn_tarmac_msg_prepare(const float* Wp, int ld, int H, int M, int K, void* tiles, uavgnn_stream_t stream) {
   if (!Wp || !tiles || H <= 0 || M <= 0 || K <= 0 || ld < 2 * H) return UAVGNN_EINVAL;
   if ((H % 32) || (ld & 3) || (reinterpret_cast<uintptr_t>(Wp) & 15) || (reinterpret_cast<uintptr_t>(tiles) & 15) || M + 2 * K > kMaxCols)
@@ -678,63 +639,27 @@ extern "C" int uavgnn_tarmac_msg_prepare(const float* Wp, int ld, int H, int M, 
 }
 
 // c_out [N, M] (row stride ld_c) always; a_save [E], proj_out [N, M + 2K], x_copy [N, H]: training outputs (each may be NULL);
-// planes_out: NULL or uavgnn_tarmac_msg_planes_bytes(N, H, M) bytes.  Every graph has exactly n_ag agents (N % n_ag == 0; 16 %
+// row_absmax [N]: NULL or the row maxima (wavefront-pair kernel only).  Every graph has exactly n_ag agents (N % n_ag == 0; 16 %
 // n_ag == 0, so no graph straddles two 16-row tiles); the rows of a tile have at most 256 in-edges, all from rows of the same tile -
 // a violating tile gets NaN messages, never a silent fallback.
 static int msg_launch(const float* x, int ld_x, const float* h, int ld_h, int N, int H, int n_ag, const void* tiles, const float* bias, int M,
                       int K, const int32_t* talk_off, const int32_t* talk_src, float scale, float* c_out, int ld_c, float* a_save,
-                      float* proj_out, int ld_p, float* x_copy, int ld_xc, void* planes_out, float* row_absmax, int dbg,
-                      uavgnn_stream_t stream);
-
-// dbg: bits 0-3 are timing ablations of tools/msg_probe.py (results are WRONG when any is set): bit 0 no weight-slice traffic
-// after the first two slices, bit 1 no MFMAs, bit 2 no activation loads after the first four slices, bit 3 no workgroup barriers;
-// bit 4 (16) selects the one-wavefront-per-row-tile kernel where the default is the wavefront-pair kernel (no planes, M + 2K <=
-// 96): correct results, the A/B reference
-extern "C" int uavgnn_tarmac_msg_fwd_dbg(const float* x, int ld_x, const float* h, int ld_h, int N, int H, int n_ag, const void* tiles,
-                                         const float* bias, int M, int K, const int32_t* talk_off, const int32_t* talk_src,
-                                         float scale, float* c_out, int ld_c, float* a_save, float* proj_out, int ld_p,
-                                         float* x_copy, int ld_xc, void* planes_out, int dbg, uavgnn_stream_t stream) {
-  return msg_launch(x, ld_x, h, ld_h, N, H, n_ag, tiles, bias, M, K, talk_off, talk_src, scale, c_out, ld_c, a_save, proj_out, ld_p, x_copy,
-                    ld_xc, planes_out, nullptr, dbg, stream);
-}
-
-static int msg_launch(const float* x, int ld_x, const float* h, int ld_h, int N, int H, int n_ag, const void* tiles, const float* bias, int M,
-                      int K, const int32_t* talk_off, const int32_t* talk_src, float scale, float* c_out, int ld_c, float* a_save,
-                      float* proj_out, int ld_p, float* x_copy, int ld_xc, void* planes_out, float* row_absmax, int dbg,
-                      uavgnn_stream_t stream) {
+                      float* proj_out, int ld_p, float* x_copy, int ld_xc, float* row_absmax, uavgnn_stream_t stream) {
   if (N < 0 || !x || !h || !tiles || !bias || !talk_off || !c_out || ld_x < H || ld_h < H || ld_c < M) return UAVGNN_EINVAL;
   if (proj_out && ld_p < M + 2 * K) return UAVGNN_EINVAL;
   if (x_copy && ld_xc < H) return UAVGNN_EINVAL;
   if (!uavgnn_tarmac_msg_supported(H, M, K, n_ag) || (N % n_ag) || (ld_x & 3) || (ld_h & 3) || (x_copy && (ld_xc & 3)) ||
       ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(tiles) |
-        reinterpret_cast<uintptr_t>(x_copy) | reinterpret_cast<uintptr_t>(planes_out)) & 15))
+        reinterpret_cast<uintptr_t>(x_copy)) & 15))
     return UAVGNN_EUNSUPPORTED;
   if (N == 0) return 0;
   const int ct = (M + 2 * K + 15) / 16;
   const bool train = a_save != nullptr || proj_out != nullptr || x_copy != nullptr;
-  const bool planes = planes_out != nullptr;
   const dim3 grid((N + kMsgRows - 1) / kMsgRows), block(kMsgThreads);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const u32x4* Wt = static_cast<const u32x4*>(tiles);
-  u32x4* po = static_cast<u32x4*>(planes_out);
-#define UAVGNN_MSG_LAUNCH(NA_, CT_, TR_, PL_)                                                                              \
-  hipLaunchKernelGGL((tarmac_msg_fwd_kernel<CT_, TR_, PL_>), grid, block, 0, st, x, ld_x, h, ld_h, N, H, n_ag, Wt, bias, M, \
-                     K, talk_off, talk_src, scale, c_out, ld_c, a_save, proj_out, ld_p, x_copy, ld_xc, po, dbg)
-#define UAVGNN_MSG_BY_FLAGS(NA_, CT_)                                    \
-  {                                                                      \
-    if (train && planes) UAVGNN_MSG_LAUNCH(NA_, CT_, true, true);        \
-    else if (train) UAVGNN_MSG_LAUNCH(NA_, CT_, true, false);            \
-    else if (planes) UAVGNN_MSG_LAUNCH(NA_, CT_, false, true);           \
-    else UAVGNN_MSG_LAUNCH(NA_, CT_, false, false);                      \
-  }
-#define UAVGNN_MSG_BY_CT(NA_)                                            \
-  {                                                                      \
-    if (ct <= 4) UAVGNN_MSG_BY_FLAGS(NA_, 4)                             \
-    else if (ct <= 6) UAVGNN_MSG_BY_FLAGS(NA_, 6)                        \
-    else UAVGNN_MSG_BY_FLAGS(NA_, 8)                                     \
-  }
-  if (row_absmax != nullptr && (planes || ct > 6 || (dbg & 31))) return UAVGNN_EUNSUPPORTED;   // written by the wavefront-pair kernel only
-  if (!planes && ct <= 6 && !(dbg & 31)) {
+  if (row_absmax != nullptr && ct > 6) return UAVGNN_EUNSUPPORTED;   // written by the wavefront-pair kernel only
+  if (ct <= 6) {
     // two wavefronts per row tile (73 KB of LDS at six column tiles: two workgroups per CU; eight column tiles would be one)
     const dim3 block2(2 * kMsgThreads);
 #define UAVGNN_MSG_K2(CT_, TR_)                                                                                                        \
@@ -756,15 +681,18 @@ static int msg_launch(const float* x, int ld_x, const float* h, int ld_h, int N,
 #undef UAVGNN_MSG_K2
     return launch_status();
   }
-  UAVGNN_MSG_BY_CT(16)
-#undef UAVGNN_MSG_BY_CT
-#undef UAVGNN_MSG_BY_FLAGS
-#undef UAVGNN_MSG_LAUNCH
+  // one wavefront per row tile, eight column tiles
+#define UAVGNN_MSG_K1(TR_)                                                                                                   \
+  hipLaunchKernelGGL((tarmac_msg_fwd_kernel<TR_>), grid, block, 0, st, x, ld_x, h, ld_h, N, H, n_ag, Wt, bias, M, K, talk_off, \
+                     talk_src, scale, c_out, ld_c, a_save, proj_out, ld_p, x_copy, ld_xc)
+  if (train) UAVGNN_MSG_K1(true);
+  else UAVGNN_MSG_K1(false);
+#undef UAVGNN_MSG_K1
   return launch_status();
 }
 
-// ... that also writes row_absmax [N] = max(|x_row|, |c_row|, |h_row|): the row scales of uavgnn_gru_cell_fwd_h2.  M + 2K <= 96, no
-// planes_out (UAVGNN_EUNSUPPORTED otherwise: the caller runs uavgnn_tarmac_msg_fwd and the bf16x3 cell)
+// ... that also writes row_absmax [N] = max(|x_row|, |c_row|, |h_row|): the row scales of uavgnn_gru_cell_fwd_h2.  M + 2K <= 96
+// (UAVGNN_EUNSUPPORTED otherwise: the caller runs uavgnn_tarmac_msg_fwd and the bf16x3 cell)
 extern "C" int uavgnn_tarmac_msg_rowmax_supported(int H, int M, int K, int n_ag) {
   return (uavgnn_tarmac_msg_supported(H, M, K, n_ag) && (M + 2 * K + 15) / 16 <= 6) ? 1 : 0;
 }
@@ -775,13 +703,13 @@ extern "C" int uavgnn_tarmac_msg_fwd_rowmax(const float* x, int ld_x, const floa
                                             float* x_copy, int ld_xc, float* row_absmax, uavgnn_stream_t stream) {
   if (!row_absmax) return UAVGNN_EINVAL;
   return msg_launch(x, ld_x, h, ld_h, N, H, n_ag, tiles, bias, M, K, talk_off, talk_src, scale, c_out, ld_c, a_save, proj_out, ld_p, x_copy,
-                    ld_xc, nullptr, row_absmax, 0, stream);
+                    ld_xc, row_absmax, stream);
 }
 
 extern "C" int uavgnn_tarmac_msg_fwd(const float* x, int ld_x, const float* h, int ld_h, int N, int H, int n_ag, const void* tiles,
                                      const float* bias, int M, int K, const int32_t* talk_off, const int32_t* talk_src,
                                      float scale, float* c_out, int ld_c, float* a_save, float* proj_out, int ld_p,
-                                     float* x_copy, int ld_xc, void* planes_out, uavgnn_stream_t stream) {
-  return uavgnn_tarmac_msg_fwd_dbg(x, ld_x, h, ld_h, N, H, n_ag, tiles, bias, M, K, talk_off, talk_src, scale, c_out, ld_c, a_save,
-                                   proj_out, ld_p, x_copy, ld_xc, planes_out, 0, stream);
+                                     float* x_copy, int ld_xc, uavgnn_stream_t stream) {
+  return msg_launch(x, ld_x, h, ld_h, N, H, n_ag, tiles, bias, M, K, talk_off, talk_src, scale, c_out, ld_c, a_save, proj_out, ld_p, x_copy,
+                    ld_xc, nullptr, stream);
 }

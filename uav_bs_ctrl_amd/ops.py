@@ -1518,8 +1518,7 @@ def _tarmac_msg_plan(x, h, Wp, bp, M, K, env, N, H):
     return tiles, n_ag
 
 
-def _launch_tarmac_msg(msg, x, h, bp, M, K, talk_off, talk_src, N, H, c_ptr, ld_c, a_save, proj, ld_p, x_copy, ld_xc, planes=None,
-                       rowmax=None):
+def _launch_tarmac_msg(msg, x, h, bp, M, K, talk_off, talk_src, N, H, c_ptr, ld_c, a_save, proj, ld_p, x_copy, ld_xc, rowmax=None):
     """rowmax [N] (optional): receives max(|x_row|, |c_row|, |h_row|) - the row scales of the f16x2 GRU cell behind this launch."""
     tiles, n_ag = msg
     if rowmax is not None:
@@ -1532,7 +1531,7 @@ def _launch_tarmac_msg(msg, x, h, bp, M, K, talk_off, talk_src, N, H, c_ptr, ld_
     with KERNEL_TIMER.span("tarmac_msg_fwd", (N, H, M, K, int(proj is not None), int(x_copy is not None))):
         rc = L.lib().uavgnn_tarmac_msg_fwd(x.data_ptr(), x.stride(0), h.data_ptr(), h.stride(0), N, H, n_ag, tiles.data_ptr(),
                                            bp.data_ptr(), M, K, L.ptr(talk_off), L.ptr(talk_src), 1.0 / K, c_ptr, ld_c, a_save, proj,
-                                           ld_p, x_copy, ld_xc, L.ptr(planes), L.stream())
+                                           ld_p, x_copy, ld_xc, L.stream())
     L.check(rc, "uavgnn_tarmac_msg_fwd")
 
 
