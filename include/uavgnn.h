@@ -628,6 +628,15 @@ int uavgnn_row_absmax(const float* a1, int ld1, int K1, const float* a2, int ld2
 int uavgnn_head_supported(int H, int A);
 int uavgnn_head_fwd(const float* h, int ld_h, int N, int H, const float* W, int ld_w, const float* b, int A, float* q, int ld_q,
                     uavgnn_stream_t stream);
+/* The dueling Q head for n_actions <= 15 (csrc/head.hip; reference: DuelingLayer.forward at algos/madrqn/agents/dueling.py:13-16, built
+ * at algos/madrqn/agents/gnn_agents.py:43-46 and called at :56): q [N, A] (row stride ld_q) = v + (adv - mean over the A columns of adv),
+ * adv = h W_adv^T + b_adv (W_adv [A, H], row stride ld_w), v = h w_v^T + b_v (w_v [H], b_v [1]).  The four parameters are read through
+ * their own pointers on every launch: no stacked copy.  Same schedule as uavgnn_head_fwd (value = column A of the 16-column tile), the
+ * combine in registers (fixed order, bit-reproducible).  H in {64, 128, 256}, 1 <= A <= 15, ld_h % 4 == 0, ld_w % 4 == 0, h, W_adv and
+ * w_v 16-byte aligned (UAVGNN_EUNSUPPORTED otherwise); a NULL pointer or a row stride below the row length: UAVGNN_EINVAL; N == 0: 0. */
+int uavgnn_head_duel_supported(int H, int A);
+int uavgnn_head_fwd_duel(const float* h, int ld_h, int N, int H, const float* W_adv, int ld_w, const float* w_v, const float* b_adv,
+                         const float* b_v, int A, float* q, int ld_q, uavgnn_stream_t stream);
 /* The recurrent half of nn.GRUCell for FEW rows (csrc/gru_rec.hip; reference: the GRU cells of the agents without a communication
  * block - algos/drqn/agents/gnn_agents.py:25-29, algos/madrqn/agents/rnn_agents.py:22-26, gnn_agents.py:29 - at 32 sequences x 1 or 8
  * agents): the input projection gi = x W_ih^T + b_ih does not depend on h, so the caller forms it for all steps of a sequence in one

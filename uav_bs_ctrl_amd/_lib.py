@@ -165,6 +165,8 @@ SIGNATURES = {
     "uavgnn_gemm_x3_supported": (_c_int, [_c_int, _c_int, _c_int]),
     "uavgnn_head_supported": (_c_int, [_c_int, _c_int]),
     "uavgnn_head_fwd": (_c_int, [_c_fp, _c_int, _c_int, _c_int, _c_fp, _c_int, _c_fp, _c_int, _c_fp, _c_int, _c_st]),
+    "uavgnn_head_duel_supported": (_c_int, [_c_int, _c_int]),
+    "uavgnn_head_fwd_duel": (_c_int, [_c_fp, _c_int, _c_int, _c_int, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_int, _c_st]),
     "uavgnn_gru_rec_supported": (_c_int, [_c_int]),
     "uavgnn_gru_rec_fwd": (_c_int, [_c_fp, _c_int, _c_fp, _c_int, _c_int, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_st]),
     "uavgnn_gru_rec_bwd": (_c_int, [_c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_int, _c_int, _c_fp, _c_fp, _c_fp, _c_fp, _c_st]),

@@ -368,8 +368,11 @@ class GnnAgent(nn.Module):
         if h.shape[0] != n:
             h = h.expand(n, -1)
         h = h.contiguous()
-        if self._comm_protocol == "tarmac" and self.f_comm._n_rounds == 1 and isinstance(self.f_out, nn.Linear):
-            return self._tarmac_step(g, x, h, dx_out)  # headline configuration: one fused autograd node per step
+        if self._comm_protocol == "tarmac" and self.f_comm._n_rounds == 1 and (
+                isinstance(self.f_out, nn.Linear) or
+                (isinstance(self.f_out, DuelingLayer) and ops.dueling_supported(h, *ops.dueling_params(self.f_out)))):
+            # headline configuration: one fused autograd node per step (a dueling head where csrc/head.hip has its form)
+            return self._tarmac_step(g, x, h, dx_out)
         if self._comm_protocol is not None:
             h = self.f_comm(g["talk"], x, h)
         else:

@@ -1,8 +1,9 @@
 """Q heads of the agent.
 
 ``DuelingLayer`` keeps the reference's parameter layout (``adv_head``, ``v_head``; algos/madrqn/agents/dueling.py:4-16)
-so checkpoints interchange, but evaluates both heads with ONE GEMM over the stacked [n_actions + 1, H] weight:
-q = V + (A - mean_a A).
+so checkpoints interchange: q = V + (A - mean_a A).  On CUDA fp32 with H in {64, 128, 256} and at most 15 actions both heads
+and the combine are ONE launch of csrc/head.hip on the live parameters (``ops.dueling_head``); everywhere else - CPU, float64,
+other shapes, ``ops.DUEL_FUSED = False`` - ONE GEMM over the stacked [n_actions + 1, H] weight and the combine in torch.
 """
 import torch as th
 import torch.nn as nn
@@ -18,6 +19,11 @@ class DuelingLayer(nn.Module):
         self.v_head = nn.Linear(in_feats, 1)
 
     def forward(self, x):
+        if x.dim() == 2 and ops.dueling_supported(x, *ops.dueling_params(self)):
+            return ops.dueling_head(x, self)
+        return self.forward_torch(x)
+
+    def forward_torch(self, x):
         w = th.cat((self.adv_head.weight, self.v_head.weight), 0)
         b = th.cat((self.adv_head.bias, self.v_head.bias), 0)
         out = ops.linear(x, w, b)                                  # [N, A + 1]: advantages | state value

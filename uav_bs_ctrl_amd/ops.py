@@ -1535,9 +1535,69 @@ def _launch_tarmac_msg(msg, x, h, bp, M, K, talk_off, talk_src, N, H, c_ptr, ld_
     L.check(rc, "uavgnn_tarmac_msg_fwd")
 
 
-def head_fwd(h, W_out, b_out):
-    """q = h W_out^T + b_out (gnn_agents.py:56), no autograd: csrc/head.hip for n_actions <= 16, else the vendor GEMM."""
+DUEL_FUSED = True   # the dueling head on csrc/head.hip and inside the fused TarMAC step; False: the torch formulation (A/B, tools/dueling_probe.py)
+
+
+def dueling_params(layer):
+    """(W_adv [A, H], b_adv [A], w_v [1, H], b_v [1]) of a DuelingLayer (agents/heads.py; dueling.py:10-11)."""
+    return layer.adv_head.weight, layer.adv_head.bias, layer.v_head.weight, layer.v_head.bias
+
+
+def dueling_fold(W_adv, b_adv, w_v, b_v):
+    """The dueling combine q = v + (adv - mean_a adv) (dueling.py:16) is linear in the two heads' outputs: q = h W_eff^T + b_eff with
+    W_eff = C W_adv + 1 w_v, b_eff = C b_adv + b_v, C = I - 1 1^T / A.  C X = X - the column means of X."""
+    return W_adv - W_adv.mean(0, keepdim=True) + w_v, b_adv - b_adv.mean() + b_v
+
+
+def dueling_split(G, g):
+    """The transpose of ``dueling_fold``: (d W_adv, d b_adv, d w_v, d b_v) from G = d W_eff = dq^T h [A, H] and g = d b_eff = colsum(dq) [A]:
+    C G, C g, 1^T G, 1^T g (C is symmetric).  Either input may be None (its two results are None then)."""
+    dWa, dwv = (None, None) if G is None else (G - G.mean(0, keepdim=True), G.sum(0, keepdim=True))
+    dba, dbv = (None, None) if g is None else (g - g.mean(), g.sum().reshape(1))
+    return dWa, dba, dwv, dbv
+
+
+def dueling_supported(h, W_adv, b_adv, w_v, b_v) -> bool:
+    """csrc/head.hip has the dueling form for this call: CUDA fp32, H in {64, 128, 256}, n_actions <= 15, DUEL_FUSED."""
+    return bool(DUEL_FUSED and h.is_cuda and h.dtype == th.float32 and h.dim() == 2 and h.shape[0] > 0 and _mc_operand(h)
+                and all(t.is_cuda and t.dtype == th.float32 and t.is_contiguous() for t in (W_adv, b_adv, w_v, b_v))
+                and W_adv.data_ptr() % 16 == 0 and w_v.data_ptr() % 16 == 0
+                and L.lib().uavgnn_head_duel_supported(h.shape[1], W_adv.shape[0]))
+
+
+def _duel_weff(W_adv, w_v):
+    """W_eff [A, H] of ``dueling_fold`` (contiguous, 16-byte aligned, no autograd history) for the backward's input gradient
+    d h = dq W_eff: three small torch launches, once per ``frozen_weights`` scope and (storage of the two weights) - per call outside."""
+    A, H = W_adv.shape
+    Wa, wv = W_adv.detach(), w_v.detach()
+
+    def build(planes):
+        out = planes.view(th.float32).view(A, H)
+        th.sub(Wa, Wa.mean(0, keepdim=True), out=out)
+        out.add_(wv)
+    planes = _cached_planes(("duel", Wa.data_ptr(), wv.data_ptr(), _version_of(W_adv), _version_of(w_v), A, H), 4 * A * H, Wa.device, build,
+                            keep=(W_adv, w_v))
+    return planes.view(th.float32).view(A, H)
+
+
+def head_fwd(h, W_out, b_out, duel=None):
+    """q = h W_out^T + b_out (gnn_agents.py:56), no autograd: csrc/head.hip for n_actions <= 16, else the vendor GEMM.
+    duel = (W_adv, b_adv, w_v, b_v): the dueling head (dueling.py:13-16) instead - W_out / b_out are not read -, csrc/head.hip for
+    n_actions <= 15, else the torch formulation."""
     N, H = h.shape
+    if duel is not None:
+        Wa, ba, wv, bv = duel
+        A = Wa.shape[0]
+        if dueling_supported(h, Wa, ba, wv, bv):
+            q = th.empty((N, A), dtype=th.float32, device=h.device)
+            with KERNEL_TIMER.span("head_fwd_duel", (N, H, A)):
+                rc = L.lib().uavgnn_head_fwd_duel(h.data_ptr(), h.stride(0), N, H, Wa.data_ptr(), Wa.stride(0), wv.data_ptr(), ba.data_ptr(),
+                                                  bv.data_ptr(), A, q.data_ptr(), A, L.stream())
+            L.check(rc, "uavgnn_head_fwd_duel")
+            return q
+        out = th.addmm(th.cat((ba, bv), 0), h, th.cat((Wa, wv), 0).t())
+        adv, val = out[:, :A], out[:, A:]
+        return val + adv - adv.mean(-1, keepdim=True)
     A = W_out.shape[0]
     if (h.is_cuda and h.dtype == th.float32 and N > 0 and _mc_operand(h) and _mc_operand(W_out)
             and b_out.is_contiguous() and L.lib().uavgnn_head_supported(H, A)):
@@ -1550,6 +1610,34 @@ def head_fwd(h, W_out, b_out):
     return th.addmm(b_out, h, W_out.t())
 
 
+class _DuelingHead(th.autograd.Function):
+    """q = v + (adv - mean_a adv) of a DuelingLayer outside the fused TarMAC step (gnn_agents._head: the agents without a communication
+    block, the other comm blocks, RnnAgent).  Forward: ONE launch of csrc/head.hip on the live parameters.  Backward: the combine is
+    linear, so d h = dq W_eff (``_duel_weff``) and the four parameter gradients are the split (``dueling_split``) of ONE product
+    G = dq^T h and one column sum - nothing per row beyond what ``ops.linear`` does for a plain head."""
+
+    @staticmethod
+    def forward(ctx, h, W_adv, b_adv, w_v, b_v):
+        ctx.save_for_backward(h, W_adv, w_v)
+        return head_fwd(h, None, None, (W_adv, b_adv, w_v, b_v))
+
+    @staticmethod
+    def backward(ctx, dq):
+        h, W_adv, w_v = ctx.saved_tensors
+        dq = L.f32c(dq)
+        dh = dWa = dba = dwv = dbv = None
+        if ctx.needs_input_grad[0]:
+            dh = _mm_nn(dq, _duel_weff(W_adv, w_v))
+        if any(ctx.needs_input_grad[1:]):
+            dWa, dba, dwv, dbv = dueling_split(_wgrad(dq, h if h.is_contiguous() else h.contiguous()), _colsum(dq))
+        return dh, dWa, dba, dwv, dbv
+
+
+def dueling_head(h, layer):
+    """The Q values of a DuelingLayer on csrc/head.hip, with autograd.  Caller checks ``dueling_supported``."""
+    return _DuelingHead.apply(h, *dueling_params(layer))
+
+
 class _TarmacStep(th.autograd.Function):
     """q, h' = head(GRU([x || c], h)), c = targeted attention over `talk` of the projections of [x || stopgrad(h)]
     (gnn_agents.py:248-271 with n_rounds = 1, then :56).  Forward: 5 vendor GEMMs + K3b + K4, the projection of the two
@@ -1558,7 +1646,9 @@ class _TarmacStep(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, h, Wp, bp, W_ih, b_ih, W_hh, b_hh, W_out, b_out, M, K, talk_off, talk_src, t_off, t_dst, t_pos,
-                split, env=None, dx_out=None, train=True):
+                split, env=None, dx_out=None, train=True, duel=None):
+        # duel = (W_adv, b_adv, w_v, b_v, identity): the dueling head (dueling.py:13-16) - the forward reads the four parameters in
+        # csrc/head.hip; W_out / b_out are then the fold W_eff / b_eff (``dueling_fold``), which is all the backward needs
         L.require_gpu(x, h, Wp, W_ih, talk_off)
         N, H = x.shape
         x, h = L.f32c(x), L.f32c(h)
@@ -1648,7 +1738,8 @@ class _TarmacStep(th.autograd.Function):
                 L.check(rc, "uavgnn_gru_gates_fwd")
             # (an accepted step that ran unfused wrote h' into a tensor of its own, not into slot t + 1: the next step's h then
             # fails the slot check above and reduces per step, like this one - ctx.seq stays None)
-        q = head_fwd(h2, W_out, b_out)
+        q = head_fwd(h2, W_out, b_out, None if duel is None else duel[:4])
+        ctx.out_id = None if duel is None else duel[4]
         if proj is None:
             proj = h2                                              # no-grad call through the fused message launch: placeholder
         ctx.dims = (M, K)
@@ -1673,7 +1764,7 @@ class _TarmacStep(th.autograd.Function):
         dx, d_proj = _step_input_grads(seq, ctx.seq_t, sink, ctx.dims, ctx.env, ctx.dx_out, proj, a_save, Wp, W_ih, W_hh,
                                        (talk_off, talk_src, (t_off, t_dst, t_pos)), d_gi, d_gh, dh, rm_g, g4)
         gWp = gbp = gWih = gbih = gWhh = gbhh = gWo = gbo = None
-        ids = {"Wp": id(Wp), "W_ih": id(W_ih), "W_hh": id(W_hh), "W_out": id(W_out)}
+        ids = {"Wp": id(Wp), "W_ih": id(W_ih), "W_hh": id(W_hh), "W_out": id(W_out) if ctx.out_id is None else ctx.out_id}
         if seq is not None:      # reduced once per sequence (WeightGradSink.end_sequence)
             seq.steps[ctx.seq_t].dq = dq      # (a reference, no copy: see _SequenceStage.dq_rows)
             seq.bwd_steps.append(ctx.seq_t)
@@ -1686,7 +1777,7 @@ class _TarmacStep(th.autograd.Function):
             gWih, gbih = _wgrad(d_gi, inp), _colsum(d_gi)
             gWhh, gbhh = _wgrad(d_gh, h), th.cat((gbih[:2 * H], _colsum(d_gh[:, 2 * H:])))
             gWo, gbo = _wgrad(dq, h2), _colsum(dq)
-        return (dx, dh, gWp, gbp, gWih, gbih, gWhh, gbhh, gWo, gbo) + (None,) * 11
+        return (dx, dh, gWp, gbp, gWih, gbih, gWhh, gbhh, gWo, gbo) + (None,) * 12
 
 
 def _step_dh2(fused_gru, sink, dq, dh2, W_out, N, H):
@@ -1815,18 +1906,22 @@ def _step_input_grads(seq, t, sink, dims, env, dx_out, proj, a_save, Wp, W_ih, W
 
 
 def tarmac_step(x, h, g, comm, f_out, stacked=None, dx_out=None):
-    """comm: the TarMAC module (f_val / f_sign / f_que / f_udt), f_out: nn.Linear head.  Returns (q, h').
+    """comm: the TarMAC module (f_val / f_sign / f_que / f_udt), f_out: nn.Linear head or a DuelingLayer (the caller checks
+    ``dueling_supported``).  Returns (q, h').
     ``stacked`` = (Wp, bp) built WITH autograd history when no GRAD_SINK will collect the weight gradients."""
     M, K = comm._msg_size, comm._key_size
     Wp, bp = stacked if stacked is not None else comm.fused_projection()
     off, src = g.talk_csc()
     cell = comm.f_udt
+    dueling = hasattr(f_out, "adv_head")
+    head_params = dueling_params(f_out) if dueling else (f_out.weight, f_out.bias)
     env = _talk_env(g, M, K)
     t_off, t_dst, t_pos = ((None, None, None) if env is not None else
-                           _talk_transpose_if_needed(g, x, h, Wp, cell.weight_ih, f_out.weight))
+                           _talk_transpose_if_needed(g, x, h, Wp, cell.weight_ih, head_params[0]))
     H = cell.weight_hh.shape[1]
-    params = {"W_ih": cell.weight_ih, "b_ih": cell.bias_ih, "W_hh": cell.weight_hh, "b_hh": cell.bias_hh,
-              "W_out": f_out.weight, "b_out": f_out.bias}
+    params = {"W_ih": cell.weight_ih, "b_ih": cell.bias_ih, "W_hh": cell.weight_hh, "b_hh": cell.bias_hh}
+    if not dueling:
+        params["W_out"], params["b_out"] = head_params
 
     def split(name, grad, col0):
         """flush target of the sink: distribute an accumulated gradient to the module's parameters."""
@@ -1849,15 +1944,35 @@ def tarmac_step(x, h, g, comm, f_out, stacked=None, dx_out=None):
             _add_grad_cols(params["b_hh"], grad[:2 * H], 0)
         elif name == "b_hh":    # the n block
             _add_grad_cols(params["b_hh"], grad, col0)
+        elif dueling and name in ("W_out", "b_out"):     # they hold d W_eff = dq^T h' / d b_eff = colsum(dq): C G | 1^T G, C g | 1^T g
+            Wa, ba, wv, bv = head_params
+            if name == "W_out":
+                dWa, _, dwv, _ = dueling_split(grad, None)
+                _add_grad(Wa, dWa)
+                _add_grad(wv, dwv)
+            else:
+                _, dba, _, dbv = dueling_split(None, grad)
+                _add_grad(ba, dba)
+                _add_grad(bv, dbv)
         else:
             _add_grad(params[name], grad)
 
     # ANY differentiable input (a trainable Q head over a frozen encoder / GRU included) makes autograd run the backward,
     # which reads the saved pre-activation sets
     train = th.is_grad_enabled() and any(t.requires_grad for t in (x, h, Wp, bp, cell.weight_ih, cell.bias_ih,
-                                                                   cell.weight_hh, cell.bias_hh, f_out.weight, f_out.bias))
-    return _TarmacStep.apply(x, h, Wp, bp, cell.weight_ih, cell.bias_ih, cell.weight_hh, cell.bias_hh, f_out.weight,
-                             f_out.bias, M, K, off, src, t_off, t_dst, t_pos, split, env, dx_out, train)
+                                                                   cell.weight_hh, cell.bias_hh) + tuple(head_params))
+    duel = None
+    if not dueling:
+        W_out, b_out = head_params
+    else:
+        Wa, ba, wv, bv = head_params
+        duel = (Wa.detach(), ba.detach(), wv.detach(), bv.detach(), id(Wa))
+        if stacked is not None:     # no sink: autograd splits the gradients of the fold back to the four parameters
+            W_out, b_out = dueling_fold(Wa, ba, wv, bv)
+        else:                       # (a no-grad call has no backward: nothing reads W_out then)
+            W_out, b_out = (_duel_weff(Wa, wv) if train else duel[0]), duel[1]
+    return _TarmacStep.apply(x, h, Wp, bp, cell.weight_ih, cell.bias_ih, cell.weight_hh, cell.bias_hh, W_out, b_out, M, K, off, src, t_off,
+                             t_dst, t_pos, split, env, dx_out, train, duel)
 
 
 class _DiscComm(th.autograd.Function):
