@@ -122,11 +122,9 @@ class _HeteroGATv2(th.autograd.Function):
                 # the parameter image of the kernel's prologue, built once per scope instead of by every workgroup of every launch
                 # (csrc/gatv2_hetero.hip, K1Image: -0.85 us of a 20-us rollout launch).  Keyed by storage AND version counters.
                 ws = pS + pN + [t for t in (brS, brN) if t is not None]
-                key = ("k1img", nh, D) + tuple(t.data_ptr() for t in ws) + tuple(t._version for t in ws)
-                image = _cached_planes(key, lib.uavgnn_gatv2_hetero_image_bytes(), x_dst.device,
+                image = _weight_planes("k1img", ws, (nh, D), lib.uavgnn_gatv2_hetero_image_bytes(),
                                        lambda buf: L.check(lib.uavgnn_gatv2_hetero_prepare(pa_s, pa_n, nh, D, NEG_SLOPE, buf.data_ptr(),
-                                                                                           L.stream()), "uavgnn_gatv2_hetero_prepare"),
-                                       keep=ws)
+                                                                                           L.stream()), "uavgnn_gatv2_hetero_prepare"))
             with KERNEL_TIMER.span("gatv2_hetero_fwd", (xs.shape[0], xn.shape[0], N, int(needS), int(needN))):
                 head = (L.ptr(xs), xs.shape[0], L.ptr(so), L.ptr(oo), L.ptr(xn), xn.shape[0], L.ptr(no), L.ptr(x_dst), N, pa_s, pa_n,
                         nh, D, NEG_SLOPE)
@@ -215,8 +213,11 @@ def hetero_gatv2(x_dst, nh, relations):
 
 
 def _version_of(t):
-    """t's version counter (None for an inference tensor, which has none)."""
-    return None if t.is_inference() else t._version
+    """t's version counter (None for an inference tensor, which has none: reading it raises)."""
+    try:
+        return t._version
+    except RuntimeError:
+        return None
 
 
 def _talk_transpose_if_needed(g, *tensors):
@@ -433,6 +434,16 @@ def _cached_planes(key, nbytes, device, build, keep=()):
     return planes
 
 
+def _weight_planes(tag, weights, dims, nbytes, build):
+    """``_cached_planes`` under THE key of a prepared form of `weights`: the tag (first: the eviction exempts "k1img"), per weight its
+    address, version counter and strides, then `dims` (the layout integers the form depends on).  The entry keeps the weights."""
+    key = [tag]
+    for W in weights:
+        key += (W.data_ptr(), _version_of(W), W.stride())
+    key += dims
+    return _cached_planes(tuple(key), nbytes, weights[0].device, build, keep=weights)
+
+
 def gru_cell_two_piece_supported(x, c, h) -> bool:
     """The bf16x3 cell takes its input as [x || c] from two buffers (no concatenated copy) when both pieces are multiples of
     32 columns wide, 16-byte aligned with row strides of whole float4s."""
@@ -457,37 +468,30 @@ def _gru_cell_launch(inp, h, W_ih, b_ih, W_hh, b_hh, save, inp2=None, h2_out=Non
     N, H = h.shape
     h2 = th.empty_like(h) if h2_out is None else h2_out
     pre = th.empty((N, 4 * H), dtype=th.float32, device=h.device) if save else None
-    if rowmax is not None:
+    if rowmax is not None or inp2 is not None or (GRU_X3 and L.lib().uavgnn_gru_cell_x3_supported(inp.shape[1], H)
+                                                  and 4 * N * max(inp.stride(0), H) < 2 ** 32):   # 32-bit byte offsets inside the kernel (3.3 M rows at K_in = 320)
         lib, K1, K2 = L.lib(), inp.shape[1], (0 if inp2 is None else inp2.shape[1])
         K_in = K1 + K2
-        with KERNEL_TIMER.span("gru_cell_fwd", (N, K_in, H, "f16x2")):
-            planes = _cached_planes(("gruh2", W_ih.data_ptr(), W_hh.data_ptr(), W_ih._version, W_hh._version, K_in, H),
-                                    lib.uavgnn_gru_cell_h2_workspace_bytes(K_in, H), h.device,
-                                    lambda p: L.check(lib.uavgnn_gru_split_weights_h2(W_ih.data_ptr(), K_in, W_hh.data_ptr(), H,
-                                                                                      p.data_ptr(), L.stream()),
-                                                      "uavgnn_gru_split_weights_h2"), keep=(W_ih, W_hh))
-            rc = lib.uavgnn_gru_cell_fwd_h2(inp.data_ptr(), inp.stride(0), K1, L.ptr(inp2), 0 if inp2 is None else inp2.stride(0), K2,
-                                            h.data_ptr(), N, H, rowmax.data_ptr(), planes.data_ptr(), b_ih.data_ptr(), b_hh.data_ptr(),
-                                            h2.data_ptr(), L.ptr(pre), L.stream())
-        L.check(rc, "uavgnn_gru_cell_fwd_h2")
-        return h2, pre
-    if inp2 is not None or (GRU_X3 and L.lib().uavgnn_gru_cell_x3_supported(inp.shape[1], H)
-                            and 4 * N * max(inp.stride(0), H) < 2 ** 32):   # 32-bit byte offsets inside the kernel (3.3 M rows at K_in = 320)
-        lib, K1, K2 = L.lib(), inp.shape[1], (0 if inp2 is None else inp2.shape[1])
-        K_in = K1 + K2
-        with KERNEL_TIMER.span("gru_cell_fwd", (N, K_in, H, "bf16x3")):
+        # the two matrix-core cells differ in their entries and in one argument: the row maxima in front of the planes (f16x2), the
+        # flag word behind the outputs (bf16x3)
+        if rowmax is not None:
+            tag, arith, ws_bytes, split, fwd = ("gruh2", "f16x2", "uavgnn_gru_cell_h2_workspace_bytes", "uavgnn_gru_split_weights_h2",
+                                                "uavgnn_gru_cell_fwd_h2")
+            scales, flags = (rowmax.data_ptr(),), ()
+        else:
+            tag, arith, ws_bytes, split, fwd = ("gru", "bf16x3", "uavgnn_gru_cell_x3_workspace_bytes", "uavgnn_gru_split_weights",
+                                                "uavgnn_gru_cell_fwd_x3_opts")
+            scales, flags = (), (GRU_X3_FLAGS,)
+        with KERNEL_TIMER.span("gru_cell_fwd", (N, K_in, H, arith)):
             # the planes are rebuilt on every call outside a frozen_weights() scope: nothing observable tells when a drop-in
             # module's weights changed
-            planes = _cached_planes(("gru", W_ih.data_ptr(), W_hh.data_ptr(), W_ih._version, W_hh._version, K_in, H),
-                                    lib.uavgnn_gru_cell_x3_workspace_bytes(K_in, H), h.device,
-                                    lambda p: L.check(lib.uavgnn_gru_split_weights(W_ih.data_ptr(), K_in, W_hh.data_ptr(), H,
-                                                                                   p.data_ptr(), L.stream()),
-                                                      "uavgnn_gru_split_weights"), keep=(W_ih, W_hh))
-            rc = lib.uavgnn_gru_cell_fwd_x3_opts(inp.data_ptr(), inp.stride(0), K1, L.ptr(inp2),
-                                                 0 if inp2 is None else inp2.stride(0), K2, h.data_ptr(), N, H, planes.data_ptr(),
-                                                 b_ih.data_ptr(), b_hh.data_ptr(), h2.data_ptr(), L.ptr(pre), GRU_X3_FLAGS,
-                                                 L.stream())
-        L.check(rc, "uavgnn_gru_cell_fwd_x3_opts")
+            planes = _weight_planes(tag, (W_ih, W_hh), (K_in, H), getattr(lib, ws_bytes)(K_in, H),
+                                    lambda p: L.check(getattr(lib, split)(W_ih.data_ptr(), K_in, W_hh.data_ptr(), H, p.data_ptr(),
+                                                                          L.stream()), split))
+            rc = getattr(lib, fwd)(inp.data_ptr(), inp.stride(0), K1, L.ptr(inp2), 0 if inp2 is None else inp2.stride(0), K2,
+                                   h.data_ptr(), N, H, *scales, planes.data_ptr(), b_ih.data_ptr(), b_hh.data_ptr(), h2.data_ptr(),
+                                   L.ptr(pre), *flags, L.stream())
+        L.check(rc, fwd)
         return h2, pre
     with KERNEL_TIMER.span("gru_cell_fwd", (N, inp.shape[1], H, "f32")):
         rc = L.lib().uavgnn_gru_cell_fwd(inp.data_ptr(), inp.stride(0), inp.shape[1], h.data_ptr(), N, H, W_ih.data_ptr(),
@@ -508,26 +512,18 @@ def _gru_gates_bwd_from_pre(pre, h, d_hout, d_gi=None, d_gh=None, head=None, sum
     if d_gh is None:
         d_gh = th.empty_like(d_gi)
     dh = th.empty_like(h)
+    # four entries over one kernel template, named by the optional outputs: _sums (+ _rowmax: the row maxima of d_gi / d_gh, `rowmax` [N],
+    # H = 256) take the head's operands whether there is a head or not (NULL, 0, NULL), _head has no optional output, the plain one neither
+    if sums is not None:
+        entry, outs = ("_sums_rowmax", (sums, rowmax)) if rowmax is not None else ("_sums", (sums,))
+    else:
+        entry, outs = ("_head" if head is not None else ""), ()
+    dq, W_out = head if head is not None else (None, None)
+    head_args = (L.ptr(dq), 0 if dq is None else dq.shape[1], L.ptr(W_out)) if entry else ()
     with KERNEL_TIMER.span("gru_gates_bwd"):
-        if sums is not None and rowmax is not None:      # ... + the row maxima of d_gi / d_gh (`rowmax` [N], H = 256)
-            dq, W_out = head if head is not None else (None, None)
-            rc = L.lib().uavgnn_gru_gates_bwd_fused_sums_rowmax(pre.data_ptr(), h.data_ptr(), L.ptr(d_hout), L.ptr(dq),
-                                                                0 if dq is None else dq.shape[1], L.ptr(W_out), N, H, d_gi.data_ptr(),
-                                                                d_gh.data_ptr(), dh.data_ptr(), sums.data_ptr(), rowmax.data_ptr(),
-                                                                L.stream())
-        elif sums is not None:
-            dq, W_out = head if head is not None else (None, None)
-            rc = L.lib().uavgnn_gru_gates_bwd_fused_sums(pre.data_ptr(), h.data_ptr(), L.ptr(d_hout), L.ptr(dq),
-                                                         0 if dq is None else dq.shape[1], L.ptr(W_out), N, H, d_gi.data_ptr(),
-                                                         d_gh.data_ptr(), dh.data_ptr(), sums.data_ptr(), L.stream())
-        elif head is not None:
-            dq, W_out = head
-            rc = L.lib().uavgnn_gru_gates_bwd_fused_head(pre.data_ptr(), h.data_ptr(), L.ptr(d_hout), dq.data_ptr(), dq.shape[1],
-                                                         W_out.data_ptr(), N, H, d_gi.data_ptr(), d_gh.data_ptr(), dh.data_ptr(),
-                                                         L.stream())
-        else:
-            rc = L.lib().uavgnn_gru_gates_bwd_fused(pre.data_ptr(), h.data_ptr(), d_hout.data_ptr(), N, H, d_gi.data_ptr(),
-                                                    d_gh.data_ptr(), dh.data_ptr(), L.stream())
+        rc = getattr(L.lib(), "uavgnn_gru_gates_bwd_fused" + entry)(pre.data_ptr(), h.data_ptr(), L.ptr(d_hout), *head_args, N, H,
+                                                                    d_gi.data_ptr(), d_gh.data_ptr(), dh.data_ptr(),
+                                                                    *(t.data_ptr() for t in outs), L.stream())
     L.check(rc, "uavgnn_gru_gates_bwd_fused")
     return d_gi, d_gh, dh
 
@@ -585,8 +581,7 @@ def gru_cell(inp, h, cell, rowmax=None):
         # ANY differentiable input makes autograd run the backward, which reads the saved [N, 4H] pre-activation sets
         train = th.is_grad_enabled() and any(t.requires_grad for t in (inp, h, cell.weight_ih, cell.bias_ih,
                                                                        cell.weight_hh, cell.bias_hh))
-        if rowmax is not None and not (GRU_H2 and GRU_X3 and L.lib().uavgnn_gru_cell_h2_supported(inp.shape[1], h.shape[1])
-                                       and 4 * inp.shape[0] * max(inp.stride(0), h.shape[1]) < 2 ** 32):
+        if rowmax is not None and not gru_cell_h2_supported(inp.shape[1], h.shape[1], inp.shape[0], inp.stride(0)):
             rowmax = None
         return _GruCellFused.apply(inp, h, cell.weight_ih, cell.bias_ih, cell.weight_hh, cell.bias_hh, train, rowmax)
     gi = linear(inp, cell.weight_ih, cell.bias_ih)
@@ -729,10 +724,9 @@ def gemm_x3(a, W, transpose_w=False, bias=None, out=None, accumulate=False, relu
     if out is None:
         out = th.empty((M, n_out), dtype=th.float32, device=a.device)
     with KERNEL_TIMER.span("gemm_x3", (M, n_out, K)):
-        planes = _cached_planes(("mat", W.data_ptr(), W._version, W.stride(0), R, C, bool(transpose_w)), 6 * R * C, a.device,
+        planes = _weight_planes("mat", (W,), (R, C, int(transpose_w)), 6 * R * C,
                                 lambda p: L.check(lib.uavgnn_split_bf16x3(W.data_ptr(), W.stride(0), R, C, int(transpose_w),
-                                                                          p.data_ptr(), L.stream()), "uavgnn_split_bf16x3"),
-                                keep=(W,))
+                                                                          p.data_ptr(), L.stream()), "uavgnn_split_bf16x3"))
         flags = GEMM_X3_FLAGS
         if not (flags & 8) and ((M + 255) // 256) * ((n_out + 127) // 128) < GEMM_X3_SMALL_GRID:
             # C2-size batches (N_a = 4096): the 256 x 128 tiles of the eight-wave kernel are 32 workgroups on 256 CUs (58 us for
@@ -764,11 +758,10 @@ def _mm_nt(x, W, b=None, relu=False):
 
 def _mm_nn(dy, W, out=None, accumulate=False, rowmax=None):
     """dy @ W (+ out when accumulate).  rowmax: the row maxima of dy from its producer -> the f16x2 kernel where it covers the shape."""
-    if rowmax is not None and gemm_h2_supported(dy, W.shape[1], W.shape[0]) and W.stride(1) == 1 and \
-            (out is None or (out.stride(1) == 1 and out.dtype == th.float32)):
+    operands_ok = W.stride(1) == 1 and (out is None or (out.stride(1) == 1 and out.dtype == th.float32))    # what both kernels ask of W / out
+    if rowmax is not None and gemm_h2_supported(dy, W.shape[1], W.shape[0]) and operands_ok:
         return gemm_h2(dy, W, rowmax, True, out=out, accumulate=accumulate)
-    if gemm_x3_supported(dy, W.shape[1], W.shape[0]) and W.stride(1) == 1 and \
-            (out is None or (out.stride(1) == 1 and out.dtype == th.float32)):
+    if gemm_x3_supported(dy, W.shape[1], W.shape[0]) and operands_ok:
         return gemm_x3(dy, W, True, out=out, accumulate=accumulate)
     if out is None:
         return th.mm(dy, W)
@@ -797,8 +790,7 @@ def gemm_x3_cat(a1, a2, W1, W2, out):
         Wc = th.cat((W1, W2), 0)                                  # [K, n_out], contiguous
         L.check(lib.uavgnn_split_bf16x3(Wc.data_ptr(), n_out, K, n_out, 1, p.data_ptr(), L.stream()), "uavgnn_split_bf16x3")
     with KERNEL_TIMER.span("gemm_x3", (M, n_out, K)):
-        planes = _cached_planes(("matcat", W1.data_ptr(), W1._version, W1.stride(0), W2.data_ptr(), W2._version, W2.stride(0), K1, K2,
-                                 n_out), 6 * K * n_out, a1.device, build, keep=(W1, W2))
+        planes = _weight_planes("matcat", (W1, W2), (K1, K2, n_out), 6 * K * n_out, build)
         rc = lib.uavgnn_gemm_nt_x3_cat(a1.data_ptr(), a1.stride(0), K1, a2.data_ptr(), a2.stride(0), M, K, planes.data_ptr(), n_out,
                                        None, out.data_ptr(), out.stride(0), GEMM_X3_FLAGS & 4, L.stream())
     L.check(rc, "uavgnn_gemm_nt_x3_cat")
@@ -829,25 +821,23 @@ def gemm_h2(a, W, rowmax, transpose_w=False, bias=None, out=None, accumulate=Fal
         assert transpose_w and W2 is not None and W.stride(1) == 1 and W2.stride(1) == 1
         K2, n_out = a2.shape[1], W.shape[1]
         K = K1 + K2
-        key = ("h2cat", W.data_ptr(), W._version, W.stride(0), W2.data_ptr(), W2._version, W2.stride(0), K1, K2, n_out)
+        tag, weights, dims = "h2cat", (W, W2), (K1, K2, n_out)
 
         def build(p):
             Wc = th.cat((W, W2), 0)                                   # [K, n_out], contiguous
             L.check(lib.uavgnn_split_h2(Wc.data_ptr(), n_out, K, n_out, 1, p.data_ptr(), L.stream()), "uavgnn_split_h2")
-        keep = (W, W2)
     else:
         R, C = W.shape
         n_out, K = (C, R) if transpose_w else (R, C)
         assert K == K1 and W.stride(1) == 1
-        key = ("h2mat", W.data_ptr(), W._version, W.stride(0), R, C, bool(transpose_w))
+        tag, weights, dims = "h2mat", (W,), (R, C, int(transpose_w))      # (gemm_h2_n64 reuses these planes: the same tag and dims there)
 
         def build(p):
             L.check(lib.uavgnn_split_h2(W.data_ptr(), W.stride(0), R, C, int(transpose_w), p.data_ptr(), L.stream()), "uavgnn_split_h2")
-        keep = (W,)
     if out is None:
         out = th.empty((M, n_out), dtype=th.float32, device=a.device)
     with KERNEL_TIMER.span("gemm_h2", (M, n_out, K)):
-        planes = _cached_planes(key, lib.uavgnn_split_h2_bytes(n_out, K), a.device, build, keep=keep)
+        planes = _weight_planes(tag, weights, dims, lib.uavgnn_split_h2_bytes(n_out, K), build)
         fn, rm2 = (lib.uavgnn_gemm_nt_h2, rowmax2) if rowmax2_out is None else (lib.uavgnn_gemm_nt_h2_rm2, rowmax2_out)
         rc = fn(a.data_ptr(), a.stride(0), K1, L.ptr(a2), 0 if a2 is None else a2.stride(0), M, K, rowmax.data_ptr(),
                 L.ptr(rm2), planes.data_ptr(), n_out, L.ptr(bias), out.data_ptr(), out.stride(0),
@@ -883,9 +873,10 @@ def gemm_h2_n64(a, W, rowmax, out=None):
     if out is None:
         out = th.empty((M, n_out), dtype=th.float32, device=a.device)
     with KERNEL_TIMER.span("gemm_h2_n64", (M, n_out, K)):
-        planes = _cached_planes(("h2mat", W.data_ptr(), W._version, W.stride(0), R, n_out, True), lib.uavgnn_split_h2_bytes(n_out, K),
-                                a.device, lambda p: L.check(lib.uavgnn_split_h2(W.data_ptr(), W.stride(0), R, n_out, 1, p.data_ptr(),
-                                                                                 L.stream()), "uavgnn_split_h2"), keep=(W,))
+        # the planes of gemm_h2(a, W, ., transpose_w=True): whichever kernel meets W first in a scope splits it for both
+        planes = _weight_planes("h2mat", (W,), (R, n_out, 1), lib.uavgnn_split_h2_bytes(n_out, K),
+                                lambda p: L.check(lib.uavgnn_split_h2(W.data_ptr(), W.stride(0), R, n_out, 1, p.data_ptr(), L.stream()),
+                                                  "uavgnn_split_h2"))
         rc = lib.uavgnn_gemm_nt_h2_n64(a.data_ptr(), a.stride(0), M, K, rowmax.data_ptr(), planes.data_ptr(), n_out, out.data_ptr(),
                                        out.stride(0), L.stream())
     L.check(rc, "uavgnn_gemm_nt_h2_n64")
@@ -913,13 +904,20 @@ def _max_two_stage(t):
     return t.reshape(S, n // S).max(1).values.max()
 
 
+def _gemm_tn_h2_shape(n, Mo, Ko, min_in=128) -> bool:
+    """csrc/gemm_tn_h2.hip (256 x 128 output tiles) takes an [Mo, Ko] = [n, Mo]^T [n, Ko] product of CUDA fp32 operands - the shape half
+    of gemm_tn_h2_supported, for a forward that asks before the gradient operand exists (_LinearReLU)."""
+    return bool(GEMM_X3 and GEMM_H2 and GEMM_TN_H2 and n >= GEMM_TN_MIN_ROWS
+                and Mo >= 256 and Ko >= min_in       # (a 9-row output leaves most of a 256 x 128 tile idle: the vendor GEMM)
+                and L.lib().uavgnn_gemm_tn_h2_supported(n, Mo, Ko))
+
+
 def gemm_tn_h2_supported(dy, x, min_in=128) -> bool:
-    """dy^T x on csrc/gemm_tn_h2.hip (256 x 128 output tiles).  min_in: the narrowest `x` worth a 128-wide tile - 128 by default; the
-    96-column projections pass 96 with the operands SWAPPED (x^T d_proj = dWp^T: three quarters of a tile instead of three eighths)."""
-    return bool(GEMM_X3 and GEMM_H2 and GEMM_TN_H2 and dy.is_cuda and dy.dtype == th.float32 and x.dtype == th.float32 and dy.dim() == 2
-                and x.dim() == 2 and dy.shape[0] == x.shape[0] and dy.shape[0] >= GEMM_TN_MIN_ROWS and _mc_operand(dy) and _mc_operand(x)
-                and dy.shape[1] >= 256 and x.shape[1] >= min_in       # (a 9-row output leaves most of a 256 x 128 tile idle: the vendor GEMM)
-                and L.lib().uavgnn_gemm_tn_h2_supported(dy.shape[0], dy.shape[1], x.shape[1]))
+    """dy^T x on csrc/gemm_tn_h2.hip.  min_in: the narrowest `x` worth a 128-wide tile - 128 by default; the 96-column projections pass
+    96 with the operands SWAPPED (x^T d_proj = dWp^T: three quarters of a tile instead of three eighths)."""
+    return bool(dy.is_cuda and dy.dtype == th.float32 and x.dtype == th.float32 and dy.dim() == 2 and x.dim() == 2
+                and dy.shape[0] == x.shape[0] and _mc_operand(dy) and _mc_operand(x)
+                and _gemm_tn_h2_shape(dy.shape[0], dy.shape[1], x.shape[1], min_in))
 
 
 def gemm_tn_x3_supported(dy, x) -> bool:
@@ -941,6 +939,52 @@ def gemm_tn_x3(dy, x, partials=None, accumulate=False):
                                    partials.shape[0], int(accumulate), L.stream())
     L.check(rc, "uavgnn_gemm_tn_x3")
     return partials
+
+
+def _wgrad_partials(dy, x, bounds=None, allow_tn=True, slot=None):
+    """[S, out, in] partials of the weight gradient dy^T x, the reduction over the rows split into S chunks (the caller sums over S, in
+    a fixed order: deterministic, no atomics) - THE place that picks the arithmetic of a weight gradient and launches it:
+    f16x2 (csrc/gemm_tn_h2.hip) when the caller hands over ``bounds`` = (bound_y, bound_x), 0-dim device tensors that bound max |.| over
+    ALL of dy / x - the column scales of the split; the caller checked ``gemm_tn_h2_supported`` (of both products of a pair, with its
+    operands swapped or not: see WeightGradSink.step_grads);
+    bf16x3 (csrc/gemm_tn_x3.hip) where ``allow_tn`` and that kernel takes the shape;
+    else the vendor's fp32 GEMM batched over ``WeightGradSink._chunks`` row chunks (a plain call leaves most CUs idle on a tiny output
+    over 10^4..10^6 rows: 400 us for 768 x 320 x 32768).
+    slot: ``slot(tag, shape) -> (partials, accumulate)`` names the buffer to launch into and whether to add to what it holds (the
+    sink's slots; tag: "tnh2", "tn" or None for the vendor product); default: a fresh buffer."""
+    n, Mo, Ko = dy.shape[0], dy.shape[1], x.shape[1]
+    if bounds is not None:
+        tag, S = "tnh2", L.lib().uavgnn_gemm_tn_h2_chunks(n, Mo, Ko)
+    elif allow_tn and gemm_tn_x3_supported(dy, x):      # (is_cuda first: the sink's host tests run on CPU tensors, without the library)
+        tag, S = "tn", L.lib().uavgnn_gemm_tn_x3_chunks(n, Mo, Ko)
+    else:
+        tag, S = None, WeightGradSink._chunks(n)
+    part, accumulate = slot(tag, (S, Mo, Ko)) if slot is not None else (None, False)
+    if part is None and tag is not None:
+        part = th.empty((S, Mo, Ko), dtype=th.float32, device=x.device)
+    if tag == "tnh2":
+        cy, cx = bounds[0].expand(Mo).contiguous(), bounds[1].expand(Ko).contiguous()
+        with KERNEL_TIMER.span("gemm_tn_h2", (n, Mo, Ko)):
+            rc = L.lib().uavgnn_gemm_tn_h2(dy.data_ptr(), dy.stride(0), Mo, x.data_ptr(), x.stride(0), Ko, n, cy.data_ptr(), cx.data_ptr(),
+                                           part.data_ptr(), S, int(accumulate), L.stream())
+        L.check(rc, "uavgnn_gemm_tn_h2")
+    elif tag == "tn":
+        gemm_tn_x3(dy, x, part, accumulate)
+    elif S > 1:         # (a buffer handed in: beta = 0 ignores what it holds)
+        xc = x if x.is_contiguous() else x.contiguous()
+        a, b = dy.view(S, n // S, -1).transpose(1, 2), xc.view(S, n // S, -1)
+        part = th.bmm(a, b) if part is None else part.baddbmm_(a, b, beta=int(accumulate))
+    elif part is None:
+        part = th.mm(dy.t(), x).unsqueeze(0)
+    else:
+        part[0].addmm_(dy.t(), x, beta=int(accumulate))
+    return part
+
+
+def _wgrad(dy, x, bounds=None):
+    """dy^T x: ``_wgrad_partials`` into a fresh buffer, then the sum over the chunks."""
+    part = _wgrad_partials(dy, x, bounds)
+    return part[0] if part.shape[0] == 1 else part.sum(0)
 
 
 class _LinearSplitK(th.autograd.Function):
@@ -967,28 +1011,10 @@ class _LinearSplitK(th.autograd.Function):
         dx = dW = db = None
         if ctx.needs_input_grad[0]:
             dx = _mm_nn(dy, W, rowmax=rowmax)
-        if ctx.needs_input_grad[1] and rowmax is not None and x_rowmax is not None and gemm_tn_h2_supported(dy, x):
-            # f16x2 weight gradient: the global maxima of the producers' row maxima bound every column (see WeightGradSink.end_sequence)
-            lib = L.lib()
-            n, Mo, Ko = dy.shape[0], dy.shape[1], x.shape[1]
-            S = lib.uavgnn_gemm_tn_h2_chunks(n, Mo, Ko)
-            part = th.empty((S, Mo, Ko), dtype=th.float32, device=x.device)
-            cy, cx = _max_two_stage(rowmax).expand(Mo).contiguous(), _max_two_stage(x_rowmax).expand(Ko).contiguous()
-            with KERNEL_TIMER.span("gemm_tn_h2", (n, Mo, Ko)):
-                rc = lib.uavgnn_gemm_tn_h2(dy.data_ptr(), dy.stride(0), Mo, x.data_ptr(), x.stride(0), Ko, n, cy.data_ptr(), cx.data_ptr(),
-                                           part.data_ptr(), S, 0, L.stream())
-            L.check(rc, "uavgnn_gemm_tn_h2")
-            dW = part.sum(0)
-        elif ctx.needs_input_grad[1] and gemm_tn_x3_supported(dy, x):
-            dW = gemm_tn_x3(dy, x).sum(0)
-        elif ctx.needs_input_grad[1]:
-            n, S = x.shape[0], WeightGradSink._chunks(x.shape[0])
-            if S > 1:
-                xc = x if x.is_contiguous() else x.contiguous()
-                part = th.bmm(dy.view(S, n // S, -1).transpose(1, 2), xc.view(S, n // S, -1))   # [S, out, in]
-                dW = part.sum(0)
-            else:
-                dW = th.mm(dy.t(), x)
+        if ctx.needs_input_grad[1]:
+            # f16x2 where the producers left row maxima: their global maxima bound every column (see WeightGradSink.step_grads)
+            h2 = rowmax is not None and x_rowmax is not None and gemm_tn_h2_supported(dy, x)
+            dW = _wgrad(dy, x, (_max_two_stage(rowmax), _max_two_stage(x_rowmax)) if h2 else None)
         if has_bias and ctx.needs_input_grad[2]:
             db = _colsum(dy)
         return dx, dW, db
@@ -1071,8 +1097,7 @@ class _LinearReLU(th.autograd.Function):
             ctx.save_for_backward(x, W, y)
             return y
         if (ctx.needs_input_grad[1] and n_out % 4 == 0 and gemm_x3_supported(x, n_out, W.shape[1]) and W.stride(1) == 1 and b is not None
-                and b.is_contiguous() and x.shape[0] >= GEMM_TN_MIN_ROWS and GEMM_TN_H2 and GEMM_H2 and n_out >= 256 and x.shape[1] >= 128
-                and L.lib().uavgnn_gemm_tn_h2_supported(x.shape[0], n_out, x.shape[1])):
+                and b.is_contiguous() and _gemm_tn_h2_shape(x.shape[0], n_out, x.shape[1])):
             # time-batched training forward: the layer's weight gradient will run on the f16x2 kernel - the bound of its X operand (this
             # x) is a by-product of this GEMM's staging
             ctx.x_rowmax = th.empty(x.shape[0], dtype=th.float32, device=x.device)
@@ -1232,44 +1257,23 @@ class WeightGradSink:
             S *= 2
         return S
 
-    def weight(self, key, dy, x, flush_fn, allow_tn=True):
-        """buffer[S, out, in] += chunked dy^T x"""
-        if allow_tn and gemm_tn_x3_supported(dy, x):      # bf16x3 kernel: accumulates into its own [S, out, in] partials in place
-            S = L.lib().uavgnn_gemm_tn_x3_chunks(x.shape[0], dy.shape[1], x.shape[1])
-            key = (key, "tn", S)
-            slot = self.slots.get(key)
-            if slot is None:
-                buf = th.zeros((S, dy.shape[1], x.shape[1]), dtype=th.float32, device=x.device)
-                self.slots[key] = slot = (buf, flush_fn)
-            gemm_tn_x3(dy, x, slot[0], accumulate=True)
-            return
-        n, S = x.shape[0], self._chunks(x.shape[0])
-        key = (key, S)          # one slot per chunk count: a change of N mid-accumulation never drops a partial sum
-        slot = self.slots.get(key)
-        if slot is None:
-            buf = th.zeros((S, dy.shape[1], x.shape[1]), dtype=th.float32, device=x.device)
-            self.slots[key] = slot = (buf, flush_fn)
-        if S == 1:
-            slot[0][0].addmm_(dy.t(), x)
-        else:
-            slot[0].baddbmm_(dy.view(S, n // S, -1).transpose(1, 2), x.view(S, n // S, -1))
+    def weight(self, key, dy, x, flush_fn, allow_tn=True, bounds=None):
+        """buffer[S, out, in] += chunked dy^T x (``_wgrad_partials``; bounds: the f16x2 kernel - the caller checked
+        gemm_tn_h2_supported).  One slot per arithmetic and chunk count: a change of N mid-accumulation never drops a partial sum."""
+        def slot(tag, shape):
+            k = (key, shape[0]) if tag is None else (key, tag, shape[0])
+            have = self.slots.get(k)
+            if have is not None:
+                return have[0], True
+            # the vendor product and the bf16x3 kernel add to zeros; the f16x2 kernel's first launch writes an uninitialised buffer
+            first = tag == "tnh2"
+            self.slots[k] = ((th.empty if first else th.zeros)(shape, dtype=th.float32, device=x.device), flush_fn)
+            return self.slots[k][0], not first
+        _wgrad_partials(dy, x, bounds, allow_tn, slot)
 
     def weight_h2(self, key, dy, x, bound_y, bound_x, flush_fn):
-        """buffer[S, out, in] += chunked dy^T x on the f16x2 kernel (csrc/gemm_tn_h2.hip).  bound_y / bound_x: 0-dim device tensors, upper
-        bounds of max |.| over ALL of dy / x - the column scales of the split (see gemm_tn_h2_supported)."""
-        lib = L.lib()
-        n, Mo, Ko = dy.shape[0], dy.shape[1], x.shape[1]
-        S = lib.uavgnn_gemm_tn_h2_chunks(n, Mo, Ko)
-        key = (key, "tnh2", S)
-        slot = self.slots.get(key)
-        acc = slot is not None
-        if slot is None:
-            self.slots[key] = slot = (th.empty((S, Mo, Ko), dtype=th.float32, device=x.device), flush_fn)
-        cy, cx = bound_y.expand(Mo).contiguous(), bound_x.expand(Ko).contiguous()
-        with KERNEL_TIMER.span("gemm_tn_h2", (n, Mo, Ko)):
-            rc = lib.uavgnn_gemm_tn_h2(dy.data_ptr(), dy.stride(0), Mo, x.data_ptr(), x.stride(0), Ko, n, cy.data_ptr(), cx.data_ptr(),
-                                       slot[0].data_ptr(), S, int(acc), L.stream())
-        L.check(rc, "uavgnn_gemm_tn_h2")
+        """``weight`` on the f16x2 kernel, as the probes call it (tools/h2_pmc_run.py)."""
+        self.weight(key, dy, x, flush_fn, bounds=(bound_y, bound_x))
 
     def bias(self, key, dy, flush_fn):
         """buffer[S, out] += row-blocked column sums of dy: one streaming HIP pass per matrix (csrc/colsum.hip), in
@@ -1349,23 +1353,21 @@ class WeightGradSink:
             # (d_proj^T x would fill three eighths of two: slower than the vendor) - 0.93 -> 0.5 ms each against the vendor's 0.74;
             # column bounds: the message kernel's row maxima bound x and h, the per-step row maxima of d_proj (taken for the d x
             # product of the step) bound d_proj
-            bxh, bpj = _max_two_stage(rm_x), _max_two_stage(rm_p)
-            self.weight_h2(("Wp_x", ids["Wp"]), x, d_proj, bxh, bpj, lambda g: split("Wp", g.t(), 0))
-            self.weight_h2(("Wp_h", ids["Wp"]), h, d_proj, bxh, bpj, lambda g: split("Wp", g.t(), H))
+            b_wp = (_max_two_stage(rm_x), _max_two_stage(rm_p))
+            self.weight(("Wp_x", ids["Wp"]), x, d_proj, lambda g: split("Wp", g.t(), 0), bounds=b_wp)
+            self.weight(("Wp_h", ids["Wp"]), h, d_proj, lambda g: split("Wp", g.t(), H), bounds=b_wp)
         else:
             self.weight(("Wp_x", ids["Wp"]), d_proj, x, lambda g: split("Wp", g, 0), allow_tn)
             self.weight(("Wp_h", ids["Wp"]), d_proj, h, lambda g: split("Wp", g, H), allow_tn)
         self.bias(("bp", ids["Wp"]), d_proj, lambda g: split("bp", g, 0))
+        b_gates = None
         if bounds is not None and gemm_tn_h2_supported(d_gi, inp) and gemm_tn_h2_supported(d_gh, h):
             # dW_ih / dW_hh on the f16x2 kernel (177-187 TFLOP/s against the vendor's 131-143 at C3): the column scales of the split
             # come for free - the global maxima of the row maxima bound every column; a column far below the global maximum is held with
             # fewer bits (absolute error <= 2^-39 of the bound per element, averaged down over 10^6 rows: DESIGN.md section 5)
-            bx, by = _max_two_stage(rm_x), _max_two_stage(rm_g)
-            self.weight_h2(("W_ih", ids["W_ih"]), d_gi, inp, by, bx, lambda g: split("W_ih", g, 0))
-            self.weight_h2((whh_key, ids["W_hh"]), d_gh, h, by, bx, whh_flush)
-        else:
-            self.weight(("W_ih", ids["W_ih"]), d_gi, inp, lambda g: split("W_ih", g, 0), allow_tn)
-            self.weight((whh_key, ids["W_hh"]), d_gh, h, whh_flush, allow_tn)
+            b_gates = (_max_two_stage(rm_g), _max_two_stage(rm_x))
+        self.weight(("W_ih", ids["W_ih"]), d_gi, inp, lambda g: split("W_ih", g, 0), allow_tn, b_gates)
+        self.weight((whh_key, ids["W_hh"]), d_gh, h, whh_flush, allow_tn, b_gates)
         if gsum is not None:
             self.bias(("b_ih", ids["W_ih"]), gsum[:, :3 * H], lambda g: split("b_ih", g, 0))
             self.bias(("b_hh_n", ids["W_hh"]), gsum[:, 3 * H:], lambda g: split("b_hh", g, 2 * H))
@@ -1431,16 +1433,6 @@ class _SequenceStage:
         if b is None or b.shape != (self.T1 + extra, n, cols) or b.device != self.x_all.device:
             b = self.bufs[name] = th.empty((self.T1 + extra, n, cols), dtype=th.float32, device=self.x_all.device)
         return b[t]
-
-
-def _wgrad(dy, x):
-    """dy^T x with the reduction over rows split into chunks (see _LinearSplitK)."""
-    if gemm_tn_x3_supported(dy, x):
-        return gemm_tn_x3(dy, x).sum(0)
-    n, S = x.shape[0], WeightGradSink._chunks(x.shape[0])
-    if S == 1:
-        return th.mm(dy.t(), x)
-    return th.bmm(dy.view(S, n // S, -1).transpose(1, 2), x.view(S, n // S, -1)).sum(0)
 
 
 GRAD_SINK = None   # set by the learner around loss.backward(); None -> gradients are returned to autograd as usual
@@ -1511,28 +1503,22 @@ def _tarmac_msg_plan(x, h, Wp, bp, M, K, env, N, H):
             or x.data_ptr() % 16 or h.data_ptr() % 16 or x.dtype != th.float32 or Wp.dtype != th.float32):
         return None
     lib = L.lib()
-    tiles = _cached_planes(("msgw", Wp.data_ptr(), Wp._version, H, M, K), lib.uavgnn_tarmac_msg_weight_bytes(H, M, K), x.device,
+    tiles = _weight_planes("msgw", (Wp,), (H, M, K), lib.uavgnn_tarmac_msg_weight_bytes(H, M, K),
                            lambda buf: L.check(lib.uavgnn_tarmac_msg_prepare(Wp.data_ptr(), Wp.stride(0), H, M, K, buf.data_ptr(),
-                                                                            L.stream()), "uavgnn_tarmac_msg_prepare"),
-                           keep=(Wp,))
+                                                                            L.stream()), "uavgnn_tarmac_msg_prepare"))
     return tiles, n_ag
 
 
 def _launch_tarmac_msg(msg, x, h, bp, M, K, talk_off, talk_src, N, H, c_ptr, ld_c, a_save, proj, ld_p, x_copy, ld_xc, rowmax=None):
-    """rowmax [N] (optional): receives max(|x_row|, |c_row|, |h_row|) - the row scales of the f16x2 GRU cell behind this launch."""
+    """rowmax [N] (optional): receives max(|x_row|, |c_row|, |h_row|) - the row scales of the f16x2 GRU cell behind this launch (the
+    _rowmax entry: the same argument list + that pointer)."""
     tiles, n_ag = msg
-    if rowmax is not None:
-        with KERNEL_TIMER.span("tarmac_msg_fwd", (N, H, M, K, int(proj is not None), int(x_copy is not None))):
-            rc = L.lib().uavgnn_tarmac_msg_fwd_rowmax(x.data_ptr(), x.stride(0), h.data_ptr(), h.stride(0), N, H, n_ag, tiles.data_ptr(),
-                                                      bp.data_ptr(), M, K, L.ptr(talk_off), L.ptr(talk_src), 1.0 / K, c_ptr, ld_c, a_save,
-                                                      proj, ld_p, x_copy, ld_xc, rowmax.data_ptr(), L.stream())
-        L.check(rc, "uavgnn_tarmac_msg_fwd_rowmax")
-        return
+    entry, outs = ("uavgnn_tarmac_msg_fwd", ()) if rowmax is None else ("uavgnn_tarmac_msg_fwd_rowmax", (rowmax.data_ptr(),))
     with KERNEL_TIMER.span("tarmac_msg_fwd", (N, H, M, K, int(proj is not None), int(x_copy is not None))):
-        rc = L.lib().uavgnn_tarmac_msg_fwd(x.data_ptr(), x.stride(0), h.data_ptr(), h.stride(0), N, H, n_ag, tiles.data_ptr(),
-                                           bp.data_ptr(), M, K, L.ptr(talk_off), L.ptr(talk_src), 1.0 / K, c_ptr, ld_c, a_save, proj,
-                                           ld_p, x_copy, ld_xc, L.stream())
-    L.check(rc, "uavgnn_tarmac_msg_fwd")
+        rc = getattr(L.lib(), entry)(x.data_ptr(), x.stride(0), h.data_ptr(), h.stride(0), N, H, n_ag, tiles.data_ptr(), bp.data_ptr(), M, K,
+                                     L.ptr(talk_off), L.ptr(talk_src), 1.0 / K, c_ptr, ld_c, a_save, proj, ld_p, x_copy, ld_xc, *outs,
+                                     L.stream())
+    L.check(rc, entry)
 
 
 DUEL_FUSED = True   # the dueling head on csrc/head.hip and inside the fused TarMAC step; False: the torch formulation (A/B, tools/dueling_probe.py)
@@ -1575,9 +1561,7 @@ def _duel_weff(W_adv, w_v):
         out = planes.view(th.float32).view(A, H)
         th.sub(Wa, Wa.mean(0, keepdim=True), out=out)
         out.add_(wv)
-    planes = _cached_planes(("duel", Wa.data_ptr(), wv.data_ptr(), _version_of(W_adv), _version_of(w_v), A, H), 4 * A * H, Wa.device, build,
-                            keep=(W_adv, w_v))
-    return planes.view(th.float32).view(A, H)
+    return _weight_planes("duel", (W_adv, w_v), (A, H), 4 * A * H, build).view(th.float32).view(A, H)
 
 
 def head_fwd(h, W_out, b_out, duel=None):
@@ -1629,7 +1613,7 @@ class _DuelingHead(th.autograd.Function):
         if ctx.needs_input_grad[0]:
             dh = _mm_nn(dq, _duel_weff(W_adv, w_v))
         if any(ctx.needs_input_grad[1:]):
-            dWa, dba, dwv, dbv = dueling_split(_wgrad(dq, h if h.is_contiguous() else h.contiguous()), _colsum(dq))
+            dWa, dba, dwv, dbv = dueling_split(_wgrad(dq, h), _colsum(dq))
         return dh, dWa, dba, dwv, dbv
 
 
