@@ -13,15 +13,15 @@ pytestmark = pytest.mark.gpu
 EPISODES = 3
 
 
-def _multi(seed=3):
-    """'debug' map (3 UBSs x 4 GTs, episode limit 10), TarMAC, H = 32, E = 4, batch 4, a ring of 8: episode 3 wraps."""
+def _multi(seed=3, c="tarmac"):
+    """'debug' map (3 UBSs x 4 GTs, episode limit 10), TarMAC (or ``c``), H = 32, E = 4, batch 4, a ring of 8: episode 3 wraps."""
     from uav_bs_ctrl_amd.learner import MultiAgentQLearner
     from uav_bs_ctrl_amd.replay import SequenceReplay
     from uav_bs_ctrl_amd.sim import BatchedUbsCoverageEnv
     th.manual_seed(seed)
     E, Hs = 4, 32
     env = BatchedUbsCoverageEnv.from_map("debug", E, seed=11)
-    args = types.SimpleNamespace(device="cuda", hidden_size=Hs, c="tarmac", n_heads=4, n_layers=2, msg_size=8, key_size=4, n_rounds=1,
+    args = types.SimpleNamespace(device="cuda", hidden_size=Hs, c=c, n_heads=4, n_layers=2, msg_size=8, key_size=4, n_rounds=1,
                                  dueling=False, mixer=False, double_q=True, lr=1e-3, gamma=0.99, polyak=0.9, max_seq_len=None,
                                  batch_size=4, seed=seed)
     info = dict(obs_shape=dict(agent=2, ubs=2, gt=4), n_actions=env.n_actions, n_agents=env.n_agents, episode_limit=env.episode_limit)
@@ -111,6 +111,57 @@ def test_collect_only_graph_fills_the_ring_and_leaves_the_parameters():
     for t, s in zip(state, snap):
         assert th.equal(t, s), "the collect-only graph moved the learner"
     rb.check()
+
+
+def _trace_state(learner):
+    """What constructing a graph must leave as it found it: the learner's five state tensors, its generator, every comm ``rng_state``."""
+    opt = learner.optimizer
+    out = dict(params=learner.flat.flat, target=learner.flat_target, adam_m=opt.m, adam_v=opt.v, hyper=opt.hyper, gen=learner._gen.get_state())
+    for name, net in (("policy", learner.policy_net), ("target", learner.target_net)):
+        out.update({f"comm.{name}.{mn}": m.rng_state for mn, m in net.named_modules() if hasattr(m, "rng_state")})
+    return {k: v.clone() for k, v in out.items()}
+
+
+def test_constructing_graphed_update_and_cycle_leaves_no_trace():
+    """``GraphedUpdate`` and ``GraphedCycle`` run their body for real before the capture - updates that move parameters, moments and the
+    step count, DiscreteComm forwards that advance the in-kernel noise counters, ``act`` calls that draw from the generator - and put all of
+    it back: bit-identical before and after construction.  One replay of the cycle then moves every one of them (the test has teeth)."""
+    from uav_bs_ctrl_amd.graphs import GraphedCycle, GraphedUpdate
+    from uav_bs_ctrl_amd.run import seed_comm_modules
+    learner, env, _, _ = _multi(c="disc")
+    B, T, n, M = 4, 3, env.n_agents, env.n_gts
+    seed_comm_modules(learner, 77)           # the noise counters exist before the captures: there is something to restore
+    # fixed-address inputs of the cycle: a batch of T + 1 simulator steps and the observation graph of the last one
+    hold = GraphedUpdate(learner, B, T, n, M, env.p.r_comm, capture=False)
+    gen = th.Generator(device="cuda").manual_seed(5)
+    env.reset_from_map()
+    for t in range(T + 1):
+        o = env.observations()
+        hold.obs.gt[t].copy_(o["gt"]), hold.obs.ubs[t].copy_(o["ubs"]), hold.obs.agent[t].copy_(o["agent"]), hold.obs.d_u2u[t].copy_(o["d_u2u"])
+        acts = th.randint(env.n_actions, (B * n,), device="cuda", generator=gen)
+        if t < T:
+            hold.acts[t].copy_(acts.view(-1, 1))
+            hold.rews[t].copy_(env.step(acts)[1])
+    hold.h0.normal_(0.0, 0.1, generator=gen), hold.h1.normal_(0.0, 0.1, generator=gen)
+    g, h = env.graph(with_comm=True, static=True), learner.init_hidden(B)
+    keys = {"params", "target", "adam_m", "adam_v", "hyper", "gen", "comm.policy.f_comm", "comm.target.f_comm"}
+    before = _trace_state(learner)
+    assert set(before) == keys, sorted(before)
+    GraphedUpdate(learner, B, T, n, M, env.p.r_comm)
+    after = _trace_state(learner)
+    assert not [k for k in before if not th.equal(before[k], after[k])], "GraphedUpdate's warm-up left its traces"
+
+    def body():
+        _, h1 = learner.act(g, h, 0.3)
+        learner.act(g, h1, 0.3)
+        return learner.update(hold._batch())
+    cycle = GraphedCycle(learner, body)
+    after = _trace_state(learner)
+    assert not [k for k in before if not th.equal(before[k], after[k])], "GraphedCycle's warm-up left its traces"
+    out = cycle()
+    moved = _trace_state(learner)
+    assert bool(th.isfinite(out["LossQ"])) and not [k for k in before if k != "gen" and th.equal(before[k], moved[k])], \
+        "a replay of the cycle left part of the state where it was: the check above proves nothing for it"
 
 
 def test_arguments():

@@ -13,6 +13,11 @@ csrc/replay.hip) the loop that ties the calls together captures too: ``GraphedEp
 caching, commits, sampling, gathers, updates - as one graph (``Episode``: the same launches, eager).  ``Evaluation`` /
 ``GraphedEvaluation`` are the reference's ``test_agent()`` on a separate evaluation simulator with their own device random state, and
 ``stats=`` (``stats.EpochStats``) keeps the epoch's log row on the device.
+
+Every class here captures through ONE routine, ``_warm_up_and_capture``: snapshot, warm-up on a side stream, capture into a ``_Window``
+(one graph, or several in one pool when the body cuts it at a collective), snapshot back.  What a class restores, whether it
+synchronises or empties the weight-plane store before the window opens and whether the learner's generator is registered are
+arguments at its call.  The epsilon-greedy launch of all of them is ``_select``.
 """
 from __future__ import annotations
 
@@ -63,6 +68,106 @@ class _RngSnapshot:
             m.rng_state.copy_(st)
 
 
+class _Window:
+    """The capture window of ``_warm_up_and_capture``: ``graphs``, the last of which is the one being captured while ``open``.  A body
+    that holds a collective calls ``cut()`` where the collective belongs: the open graph ends there and the next one begins, in
+    the first one's memory pool, so the collective can be issued eagerly between two replays.  gen: a generator every graph of the
+    window registers (the epsilon draws of ``th.rand``); None: none is registered."""
+
+    def __init__(self, gen=None):
+        self.gen, self.graphs, self._ctx = gen, [], None
+        self._add()              # the first graph exists (and knows the generator) before the warm-up runs
+
+    def _add(self):
+        graph = th.cuda.CUDAGraph()
+        if self.gen is not None and hasattr(graph, "register_generator_state"):
+            graph.register_generator_state(self.gen)
+        self.graphs.append(graph)
+
+    @property
+    def open(self) -> bool:
+        return self._ctx is not None
+
+    def __enter__(self):
+        self._ctx = _capture(self.graphs[-1], **({"pool": self.graphs[0].pool()} if len(self.graphs) > 1 else {}))
+        self._ctx.__enter__()
+        return self
+
+    def __exit__(self, *exc):
+        ctx, self._ctx = self._ctx, None
+        return ctx.__exit__(*exc)
+
+    def cut(self):
+        self.__exit__(None, None, None)
+        self._add()
+        self.__enter__()
+
+
+def _warm_up_and_capture(warmup: int, body, window: _Window, captured=None, *, learner=None, state=None, sync: bool = False,
+                         flush: bool = False):
+    """The capture protocol of this module, once.  ``body`` runs ``warmup`` times for real on a side stream (allocator pools, lazy
+    kernels, plane caches), then ``captured`` (default: ``body``) runs once inside ``window`` - ``_capture`` on the current stream, no
+    fork or second stream inside it - and its value is returned.  What the warm-up moved is put back afterwards, so a graphed run
+    starts from the state an eager run starts from:
+
+    learner: its ``state_tensors()`` (after ``sync_lr()``: a learning rate the scheduler moved since the last sync is part of the
+        snapshot, not undone by it), its random state (``_RngSnapshot``) and, at the end, its weight-plane store (emptied: the
+        planes in it were split from the warm-up's parameters).
+    state: further tensors to clone before the warm-up and copy back after the capture.
+    Neither (None, None): nothing is restored and the device is not synchronised after the capture.
+    sync: synchronise before the window opens - collectives ran in the warm-up and must be complete.
+    flush: empty the learner's weight-plane store before the window opens, so that the graph holds the launches that build the planes
+        (whether it does changes the graph's node list)."""
+    restore = learner is not None or state is not None
+    state = list(state or ())
+    if learner is not None:
+        learner.optimizer.sync_lr()
+        state = learner.state_tensors() + state
+    snap = [t.clone() for t in state]
+    rng = None if learner is None else _RngSnapshot(learner)
+    side = th.cuda.Stream()
+    side.wait_stream(th.cuda.current_stream())
+    with th.cuda.stream(side):
+        for _ in range(warmup):
+            body()
+    th.cuda.current_stream().wait_stream(side)
+    if flush:
+        learner.invalidate_weight_cache()
+    if sync:
+        th.cuda.synchronize()
+    with window:
+        out = (captured or body)()
+    if restore:
+        th.cuda.synchronize()
+        for dst, src in zip(state, snap):
+            dst.copy_(src)
+        if learner is not None:
+            rng.restore()
+            learner.invalidate_weight_cache()
+    return out
+
+
+def _select(learner, logits: th.Tensor, eps: th.Tensor, pair: Optional[th.Tensor] = None) -> th.Tensor:
+    """Epsilon-greedy actions [N] int64 from ``logits`` [N, A] with the exploration rate in device memory (``eps``: float32 [1]): one
+    exploration draw per team of ``learner.n_agents`` rows, first maximum (learner.py:75-78).  pair: a device int64 {seed, step} -
+    the uniforms are drawn inside the kernel and the step advances by one (uavgnn_eps_greedy_philox); None - they come from
+    ``learner._gen``, one per team and one per row in ONE generator call (uavgnn_eps_greedy_dev)."""
+    N = logits.shape[0]
+    acts = th.empty(N, dtype=th.int64, device=learner.device)
+    logits = logits if logits.stride(1) == 1 else logits.contiguous()
+    if pair is not None:
+        L.check(L.lib().uavgnn_eps_greedy_philox(logits.data_ptr(), logits.stride(0), N, learner.n_actions, learner.n_agents,
+                                                 pair.data_ptr(), eps.data_ptr(), 0.0, acts.data_ptr(), L.stream()),
+                "uavgnn_eps_greedy_philox")
+    else:
+        teams = N // learner.n_agents
+        u = th.rand(teams + N, device=learner.device, generator=learner._gen)
+        L.check(L.lib().uavgnn_eps_greedy_dev(logits.data_ptr(), logits.stride(0), N, learner.n_actions, learner.n_agents,
+                                              u.data_ptr(), u.data_ptr() + 4 * teams, eps.data_ptr(), acts.data_ptr(), L.stream()),
+                "uavgnn_eps_greedy_dev")
+    return acts
+
+
 class _PaddedObs:
     """Fixed-address padded observation buffers (the simulator's format, mubs_cov.py:215-242) of ``lead`` env steps."""
 
@@ -82,38 +187,23 @@ class _PaddedObs:
 
 
 class _GraphedActBase:
-    """What the captured rollout steps share: the warm-up and capture of ``_body`` with the learner's generator registered, the
-    epsilon-greedy selection from device-resident epsilon, and the replay.  A subclass sets ``learner``, ``B`` (teams), ``h_in`` and
+    """What the captured rollout steps share: the capture of ``_body`` with the learner's generator registered, the epsilon-greedy
+    selection from device-resident epsilon, and the replay.  A subclass sets ``learner``, ``B`` (teams), ``h_in`` and
     its observation buffers, defines ``_obs()`` (the observation batch built from those buffers) and calls ``_capture_act``."""
 
     def _capture_act(self, warmup: int):
         learner = self.learner
         self.eps = th.zeros(1, dtype=th.float32, device=learner.device)
         self._eps_host = None
-        self.graph = th.cuda.CUDAGraph()
-        if hasattr(self.graph, "register_generator_state"):
-            self.graph.register_generator_state(learner._gen)
-        side = th.cuda.Stream()
-        side.wait_stream(th.cuda.current_stream())
-        with th.cuda.stream(side):              # warm-up on a side stream (allocator pools, lazy kernels) before capture
-            for _ in range(warmup):
-                self._body()
-        th.cuda.current_stream().wait_stream(side)
-        with _capture(self.graph):
-            self.acts, self.h_out = self._body()
+        window = _Window(learner._gen)
+        # nothing is restored: a rollout step moves no parameter, and the warm-up's epsilon draws and comm noise steps stay advanced
+        self.acts, self.h_out = _warm_up_and_capture(warmup, self._body, window)
+        self.graph = window.graphs[0]
 
     @th.no_grad()
     def _body(self):
-        lr = self.learner
-        logits, h = lr.policy_net(self._obs(), self.h_in)
-        N = logits.shape[0]
-        u = th.rand(self.B + N, device=lr.device, generator=lr._gen)
-        acts = th.empty(N, dtype=th.int64, device=lr.device)
-        logits = logits if logits.stride(1) == 1 else logits.contiguous()
-        L.check(L.lib().uavgnn_eps_greedy_dev(logits.data_ptr(), logits.stride(0), N, lr.n_actions, lr.n_agents,
-                                              u.data_ptr(), u.data_ptr() + 4 * self.B, self.eps.data_ptr(),
-                                              acts.data_ptr(), L.stream()), "uavgnn_eps_greedy_dev")
-        return acts, h
+        logits, h = self.learner.policy_net(self._obs(), self.h_in)
+        return _select(self.learner, logits, self.eps), h
 
     def _replay(self, h, eps_thres: float):
         if h is not None and h.data_ptr() != self.h_in.data_ptr():
@@ -202,46 +292,35 @@ class GraphedSingleUbsAct(_GraphedActBase):
 
 
 class _GraphedUpdateBase:
-    """What the captured updates share: warm-up updates run for real with parameters, target, moments, ``hyper`` and the random
-    state snapshotted and restored around them, the capture of ``learner.update(self._batch())`` - cut at the gradient
-    all-reduce into two graphs when ``learner.needs_collective()`` - and the replay.  A subclass sets ``learner`` and its
-    fixed-address input buffers, defines ``_batch()`` / ``load(m)`` and calls ``_capture_update``."""
+    """What the captured updates share: the capture of ``learner.update(self._batch())`` - the learner's state restored after the
+    warm-up updates, the window cut at the gradient all-reduce into two graphs when ``learner.needs_collective()`` - the replay and
+    ``load_from``.  A subclass sets ``learner`` and its fixed-address input buffers, defines ``_batch()`` / ``load(m)`` and calls
+    ``_capture_update``."""
 
     def _capture_update(self, warmup: int):
         learner = self.learner
         assert learner.fused_tail, "graph capture needs the device-resident update tail (CUDA learner)"
-        self.graph = th.cuda.CUDAGraph()
-        # warm-up updates run for real (they would move the parameters): snapshot and restore around them
-        learner.optimizer.sync_lr()      # a learning rate the scheduler moved since the last sync is part of the snapshot, not undone by it
-        snap = [t.clone() for t in (learner.flat.flat, learner.flat_target, learner.optimizer.m, learner.optimizer.v,
-                                    learner.optimizer.hyper)]
-        rng = _RngSnapshot(learner)
         self.split = learner.needs_collective()
-        side = th.cuda.Stream()
-        side.wait_stream(th.cuda.current_stream())
-        with th.cuda.stream(side):
-            for _ in range(warmup):
-                self._body()
-        th.cuda.current_stream().wait_stream(side)
+        window = _Window()               # the generator is not registered: an update draws nothing from it
+
+        def cut_body():                  # the update without its collective: `accumulate` | `apply`
+            out = learner.accumulate(self._batch())
+            window.cut()
+            learner.apply()
+            return out
+        # the weight-plane store is not emptied before the window: the planes are built inside `accumulate`'s own store either way
+        self.out = _warm_up_and_capture(warmup, self._body, window, cut_body if self.split else None, learner=learner, sync=self.split)
+        self.graph = window.graphs[0]
         if self.split:
-            th.cuda.synchronize()          # the warm-up updates' all-reduces are complete before a capture window opens
-            self.graph_tail = th.cuda.CUDAGraph()
-            with _capture(self.graph):
-                self.out = self.learner.accumulate(self._batch())
-            with _capture(self.graph_tail, pool=self.graph.pool()):
-                self.learner.apply()
-        else:
-            with _capture(self.graph):
-                self.out = self._body()
-        th.cuda.synchronize()
-        for dst, src in zip((learner.flat.flat, learner.flat_target, learner.optimizer.m, learner.optimizer.v,
-                             learner.optimizer.hyper), snap):
-            dst.copy_(src)
-        rng.restore()
-        learner.invalidate_weight_cache()
+            self.graph_tail = window.graphs[1]
 
     def _body(self) -> Dict:
         return self.learner.update(self._batch())
+
+    def load_from(self, replay, idx: th.Tensor) -> None:
+        """The sequences ``idx`` of a device-state replay straight from its ring into the graph's buffers: ONE gather launch
+        (``replay.gather_into``) instead of one ``index_select`` and one copy per field.  Same bits as ``load``."""
+        replay.gather_into(idx, self)
 
     def __call__(self, m: Optional[Dict[str, th.Tensor]] = None) -> Dict:
         if m is not None:
@@ -321,11 +400,6 @@ class GraphedUpdate(_GraphedUpdateBase):
         if self.states is not None:
             self.states.copy_(m["state"].transpose(0, 1), non_blocking=True)
 
-    def load_from(self, replay, idx: th.Tensor) -> None:
-        """The sequences ``idx`` of a device-state replay straight from its ring into the graph's buffers: ONE gather launch
-        (``replay.gather_into``) instead of one ``index_select`` and one copy per field.  Same bits as ``load``."""
-        replay.gather_into(idx, self)
-
 
 class GraphedSingleUbsUpdate(_GraphedUpdateBase):
     """``QLearner.update`` on B stored sequences of T transitions of the single-UBS environment (experiment 1) as one graph replay:
@@ -375,11 +449,6 @@ class GraphedSingleUbsUpdate(_GraphedUpdateBase):
         self.rews.copy_(m["rew"].transpose(0, 1), non_blocking=True)
         self.dones.copy_(m["done"].transpose(0, 1), non_blocking=True)
 
-    def load_from(self, replay, idx: th.Tensor) -> None:
-        """The sequences ``idx`` of a device-state replay straight from its ring into the graph's buffers: ONE gather launch
-        (``replay.gather_into``) instead of one ``index_select`` and one copy per field.  Same bits as ``load``."""
-        replay.gather_into(idx, self)
-
 
 class GraphedCycle:
     """A whole acting / training cycle on FIXED-ADDRESS inputs - e.g. T ``learner.act`` calls on stored graphs followed by one
@@ -399,29 +468,10 @@ class GraphedCycle:
         assert learner.fused_tail, "graph capture needs the device-resident update tail (CUDA learner)"
         assert not learner.needs_collective(), "a data-parallel update cannot be captured whole: use GraphedUpdate"
         self.learner, self.body = learner, body
-        self.graph = th.cuda.CUDAGraph()
-        if hasattr(self.graph, "register_generator_state"):
-            self.graph.register_generator_state(learner._gen)
-        # the warm-up cycles run for real (an update inside `body` moves the parameters): snapshot and restore around them, so a
-        # graphed run starts from the state an eager run starts from
-        learner.optimizer.sync_lr()      # a learning rate the scheduler moved since the last sync is part of the snapshot, not undone by it
-        state = (learner.flat.flat, learner.flat_target, learner.optimizer.m, learner.optimizer.v, learner.optimizer.hyper)
-        snap = [t.clone() for t in state]
-        rng = _RngSnapshot(learner)      # the warm-up's epsilon draws and DiscreteComm noise steps are undone as well
-        side = th.cuda.Stream()
-        side.wait_stream(th.cuda.current_stream())
-        with th.cuda.stream(side):
-            for _ in range(warmup):
-                body()
-        th.cuda.current_stream().wait_stream(side)
-        learner.invalidate_weight_cache()
-        with _capture(self.graph):
-            self.out = body()
-        th.cuda.synchronize()
-        for dst, src in zip(state, snap):
-            dst.copy_(src)
-        rng.restore()
-        learner.invalidate_weight_cache()
+        window = _Window(learner._gen)
+        # flush: `learner.act` calls in `body` keep their planes in the learner's store, and the graph must hold the launches that build them
+        self.out = _warm_up_and_capture(warmup, body, window, learner=learner, flush=True)
+        self.graph = window.graphs[0]
 
     def __call__(self):
         self.learner.optimizer.sync_lr()
@@ -433,9 +483,30 @@ class GraphedCycle:
 INFO_KEYS = ("EpRet", "EpLen", "AvgGlobalUtility", "TotalThroughput", "FairIdx", "ProbCollision")
 
 
+def info_keys(single: bool):
+    """The statistics ``env.step`` returns (run.py:93 ``logger.store(**info)``; ProbCollision: the multi-UBS simulator only)."""
+    return INFO_KEYS[:-1] if single else INFO_KEYS
+
+
 class _EnvObs:
-    """The policy's observation batch straight from a device simulator's output buffers.  A subclass sets ``env``, ``single``, ``enc``
-    and, for the multi-UBS simulator, ``_build`` / ``with_comm``."""
+    """Which device simulator an episode or an evaluation runs on, decided once by ``_bind_env``: ``single`` (experiment 1), ``keys``
+    (its info keys), ``_reset`` (its reset on the device) and, for the multi-UBS simulator, ``_build`` / ``with_comm``; ``_obs()`` is
+    the policy's observation batch straight from its output buffers.  ``env.reset_rng`` is the reset counter of either."""
+
+    def _bind_env(self, learner, env, enc: str) -> None:
+        from .sim import BatchedSingleUbsCoverageEnv
+        self.env, self.enc = env, enc
+        self.single = isinstance(env, BatchedSingleUbsCoverageEnv)
+        self.keys = info_keys(self.single)
+        if self.single:
+            _single_ubs_enc(enc)
+            self._reset = env.reset
+        else:
+            self._build = _builder(enc)
+            if env.spec is None:
+                raise ValueError("env: an environment with a map expected (BatchedUbsCoverageEnv.from_map): the reset draws on the device")
+            self.with_comm = learner.args.c is not None
+            self._reset = env.reset_from_map
 
     def _obs(self):
         o = self.env.out
@@ -443,10 +514,6 @@ class _EnvObs:
             return o["obs_flat"] if self.enc == "rnn" else from_single_ubs_obs(o["obs_gt"], o["obs_agent"])
         return self._build(o["obs_gt"], o["obs_ubs"], o["obs_agent"], o["d_u2u"] if self.with_comm else None, self.env.p.r_comm,
                            static=True)
-
-    def _info_keys(self):
-        """The statistics ``env.step`` returns (run.py:93 ``logger.store(**info)``; ProbCollision: the multi-UBS simulator only)."""
-        return tuple(k for k in INFO_KEYS if not (self.single and k == "ProbCollision"))
 
 
 class Episode(_EnvObs):
@@ -479,11 +546,9 @@ class Episode(_EnvObs):
 
     def __init__(self, learner, env, replay, batch_size: int, eps=(1.0, 0.05, 5e4), train: bool = True,
                  updates_per_segment: int = 1, enc: str = "gnn", stats=None, explore_seed: Optional[int] = None):
-        from .sim import BatchedSingleUbsCoverageEnv
         assert learner.fused_tail, "the device loop needs the device-resident update tail (CUDA learner)"
-        self.learner, self.env, self.replay, self.batch_size = learner, env, replay, int(batch_size)
-        self.train, self.updates_per_segment, self.enc = bool(train), int(updates_per_segment), enc
-        self.single = isinstance(env, BatchedSingleUbsCoverageEnv)
+        self.learner, self.replay, self.batch_size = learner, replay, int(batch_size)
+        self.train, self.updates_per_segment = bool(train), int(updates_per_segment)
         if not getattr(replay, "device_state", False):
             raise ValueError("replay: a device-state replay expected (device_state=True)")
         if replay.n_envs != env.B:
@@ -500,14 +565,10 @@ class Episode(_EnvObs):
         if not self.decay_steps > 0:
             raise ValueError("eps = (start, end, decay_steps): decay_steps must be positive")
         dev = learner.device
+        self._bind_env(learner, env, enc)
         if self.single:
-            _single_ubs_enc(enc)
             self.upd = GraphedSingleUbsUpdate(learner, self.batch_size, self.T, env.n_gts, enc, capture=False) if self.train else None
         else:
-            self._build = _builder(enc)
-            if env.spec is None:
-                raise ValueError("env: an environment with a map expected (BatchedUbsCoverageEnv.from_map): the reset draws on the device")
-            self.with_comm = learner.args.c is not None
             self.with_state = replay.mem["state"].shape[-1] > 0
             if getattr(learner, "mixer", None) is not None:      # QMIX: q_tot is one value per environment, mixed from the stored global state
                 sd, rd = replay.mem["state"].shape[-1], replay.mem["rew"].shape[-1]
@@ -528,7 +589,7 @@ class Episode(_EnvObs):
         self.out: Optional[Dict] = None
         self.stats, self.info = stats, None
         if stats is not None:
-            missing = [k for k in self._info_keys() + (("LossQ",) if self.train else ()) if k not in stats.index]
+            missing = [k for k in self.keys + (("LossQ",) if self.train else ()) if k not in stats.index]
             if missing:
                 raise ValueError(f"stats: keys {missing} are missing")
 
@@ -546,18 +607,7 @@ class Episode(_EnvObs):
         L.check(L.lib().uavgnn_eps_schedule(self.t.data_ptr(), E, self.eps_start, self.eps_end, self.decay_steps,
                                             self.eps.data_ptr(), L.stream()), "uavgnn_eps_schedule")
         logits, h2 = lr.policy_net(self._obs(), h)
-        N = logits.shape[0]
-        acts = th.empty(N, dtype=th.int64, device=lr.device)
-        logits = logits if logits.stride(1) == 1 else logits.contiguous()
-        if self.explore is not None:
-            L.check(L.lib().uavgnn_eps_greedy_philox(logits.data_ptr(), logits.stride(0), N, lr.n_actions, lr.n_agents,
-                                                     self.explore.data_ptr(), self.eps.data_ptr(), 0.0, acts.data_ptr(), L.stream()),
-                    "uavgnn_eps_greedy_philox")
-        else:
-            u = th.rand(E + N, device=lr.device, generator=lr._gen)
-            L.check(L.lib().uavgnn_eps_greedy_dev(logits.data_ptr(), logits.stride(0), N, lr.n_actions, lr.n_agents, u.data_ptr(),
-                                                  u.data_ptr() + 4 * E, self.eps.data_ptr(), acts.data_ptr(), L.stream()),
-                    "uavgnn_eps_greedy_dev")
+        acts = _select(lr, logits, self.eps, self.explore)
         o2, rew, done, info = env.step(acts)
         if self.single:
             lr.cache(rb, None, None, acts, rew, o2, h2, done, info["BadMask"], staged=True)
@@ -573,8 +623,8 @@ class Episode(_EnvObs):
         return self.learner.update(batch)
 
     def _body(self) -> Optional[Dict]:
-        lr, env, rb = self.learner, self.env, self.replay
-        env.reset() if self.single else env.reset_from_map()
+        rb = self.replay
+        self._reset()
         h, out = self.h_zero, None
         for _ in range(self.segments):
             with ops.frozen_weights():        # nothing moves a parameter inside a segment's rollout: weight planes are split once
@@ -589,7 +639,7 @@ class Episode(_EnvObs):
                     if self.stats is not None:
                         self.stats.push(LossQ=out["LossQ"])
         if self.stats is not None:
-            self.stats.push(**{k: self.info[k] for k in self._info_keys()})
+            self.stats.push(**{k: self.info[k] for k in self.keys})
         return out
 
     def __call__(self) -> Optional[Dict]:
@@ -627,65 +677,24 @@ class GraphedEpisode(Episode):
         collective = learner.needs_collective()
         self.split = self.train and collective
         self.collectives_per_replay = self.segments * self.updates_per_segment if self.split else 0
-        self._window = None                # the open capture window while the cut body is being captured
-        self.graph = self._new_graph()
-        self.graphs = [self.graph]
-        learner.optimizer.sync_lr()      # a learning rate the scheduler moved since the last sync is part of the snapshot, not undone by it
-        env_rng = env.rng if self.single else env.map_rng
-        state = (learner.flat.flat, learner.flat_target, learner.optimizer.m, learner.optimizer.v, learner.optimizer.hyper,
-                 replay.state, replay.rng, replay.status, self.t, self.eps, env_rng)
+        self._window = _Window(learner._gen)           # every piece registers the generator
+        self.graphs = self._window.graphs
+        self.graph = self.graphs[0]
+        state = [replay.state, replay.rng, replay.status, self.t, self.eps, env.reset_rng]
         if self.explore is not None:
-            state += (self.explore,)
+            state.append(self.explore)
         if stats is not None:
-            state += tuple(stats.state_tensors())      # the warm-up episodes' pushes are undone as well
-        snap = [t.clone() for t in state]
-        rng = _RngSnapshot(learner)
-        side = th.cuda.Stream()
-        side.wait_stream(th.cuda.current_stream())
-        with th.cuda.stream(side):
-            for _ in range(warmup):
-                self._body()
-        th.cuda.current_stream().wait_stream(side)
-        learner.invalidate_weight_cache()
-        if collective:
-            th.cuda.synchronize()          # the warm-up episodes' all-reduces are complete before a capture window opens
-        if self.split:
-            self._window = _capture(self.graph)
-            self._window.__enter__()
-            try:
-                self.out = self._body()    # `_update` closes the window after each `accumulate` and opens the next graph's
-            except BaseException:
-                import sys
-                self._window.__exit__(*sys.exc_info())
-                raise
-            else:
-                self._window.__exit__(None, None, None)
-            finally:
-                self._window = None
-            assert len(self.graphs) == self.collectives_per_replay + 1
-        else:
-            with _capture(self.graph):
-                self.out = self._body()
-        th.cuda.synchronize()
-        for dst, src in zip(state, snap):
-            dst.copy_(src)
-        rng.restore()
-        learner.invalidate_weight_cache()
-
-    def _new_graph(self):
-        graph = th.cuda.CUDAGraph()
-        if hasattr(graph, "register_generator_state"):
-            graph.register_generator_state(self.learner._gen)
-        return graph
+            state += stats.state_tensors()             # the warm-up episodes' pushes are undone as well
+        # flush: as GraphedCycle (the body's stores are its own, so nothing of the learner's store is read); sync: whenever the learner
+        # holds a collective, also with train=False, whose warm-up ran none
+        self.out = _warm_up_and_capture(warmup, self._body, self._window, learner=learner, state=state, sync=collective, flush=True)
+        assert len(self.graphs) == self.collectives_per_replay + 1
 
     def _update(self, batch) -> Dict:
-        if self._window is None:           # warm-up, or a run without a collective: the whole update
+        if not (self.split and self._window.open):     # warm-up, or a run without a collective: the whole update
             return super()._update(batch)
         out = self.learner.accumulate(batch)
-        self._window.__exit__(None, None, None)      # the cut: this graph ends on the gradient, the next begins with `apply`
-        self.graphs.append(self._new_graph())
-        self._window = _capture(self.graphs[-1], pool=self.graph.pool())
-        self._window.__enter__()
+        self._window.cut()                 # this graph ends on the gradient, the next begins with `apply`
         self.learner.apply()
         return out
 
@@ -725,9 +734,7 @@ class Evaluation(_EnvObs):
 
     def __init__(self, learner, env, episodes: int, eps: float = 0.05, seed: int = 0, enc: str = "gnn", stats=None,
                  prefix: str = "Test", film=None):
-        from .sim import BatchedSingleUbsCoverageEnv
-        self.learner, self.env, self.enc, self.stats, self.prefix, self.film = learner, env, enc, stats, prefix, film
-        self.single = isinstance(env, BatchedSingleUbsCoverageEnv)
+        self.learner, self.stats, self.prefix, self.film = learner, stats, prefix, film
         self.episodes = int(episodes)
         if self.episodes < 1 or self.episodes % env.B != 0:
             raise ValueError(f"episodes = {episodes} is no positive multiple of the simulator's {env.B} environments")
@@ -736,20 +743,12 @@ class Evaluation(_EnvObs):
             if film.episodes != self.episodes:
                 raise ValueError(f"film: it holds {film.episodes} episodes, the evaluation runs {self.episodes}")
             film.match(env)
-        if self.single:
-            _single_ubs_enc(enc)
-        else:
-            self._build = _builder(enc)
-            if env.spec is None:
-                raise ValueError("env: an environment with a map expected (BatchedUbsCoverageEnv.from_map): the reset draws on the device")
-            self.with_comm = learner.args.c is not None
-        self.keys = self._info_keys()
+        self._bind_env(learner, env, enc)
         if stats is not None:
             missing = [prefix + k for k in self.keys if prefix + k not in stats.index]
             if missing:
                 raise ValueError(f"stats: keys {missing} are missing")
         dev = learner.device
-        self.n_agents = 1 if self.single else env.n_agents
         # built here, outside any capture (host-to-device copies)
         self.h_zero = learner.init_hidden(env.B)
         self.eps = th.tensor([float(eps)], dtype=th.float32, device=dev)
@@ -759,16 +758,6 @@ class Evaluation(_EnvObs):
 
     def _comm_modules(self):
         return [m for m in self.learner.policy_net.modules() if hasattr(m, "rng_state")]
-
-    def _select(self, logits: th.Tensor) -> th.Tensor:
-        lr = self.learner
-        N = logits.shape[0]
-        acts = th.empty(N, dtype=th.int64, device=lr.device)
-        logits = logits if logits.stride(1) == 1 else logits.contiguous()
-        L.check(L.lib().uavgnn_eps_greedy_philox(logits.data_ptr(), logits.stride(0), N, lr.n_actions, self.n_agents,
-                                                 self.rng.data_ptr(), self.eps.data_ptr(), 0.0, acts.data_ptr(), L.stream()),
-                "uavgnn_eps_greedy_philox")
-        return acts
 
     def _comm_save(self):
         """The policy's comm ``rng_state``s before the rounds: device copies of the ones that exist; for a module that was never
@@ -797,13 +786,13 @@ class Evaluation(_EnvObs):
         lr, env, B, film = self.learner, self.env, self.env.B, self.film
         with ops.frozen_weights():            # a store of this call's own: the learner's rollout store is not touched
             for r in range(self.rounds):
-                env.reset() if self.single else env.reset_from_map()
+                self._reset()
                 if film is not None:
                     film.reload(env, r * B)
                 h, info = self.h_zero, None
                 for _ in range(env.episode_limit):
                     logits, h = lr.policy_net(self._obs(), h)
-                    acts = self._select(logits)
+                    acts = _select(lr, logits, self.eps, self.rng)
                     _, _, _, info = env.step(acts)
                     if film is not None:
                         film.click(env, acts, r * B)
@@ -836,29 +825,21 @@ class GraphedEvaluation(Evaluation):
     def __init__(self, learner, env, episodes: int, eps: float = 0.05, seed: int = 0, enc: str = "gnn", stats=None,
                  prefix: str = "Test", warmup: int = 2, film=None):
         super().__init__(learner, env, episodes, eps, seed, enc, stats, prefix, film)
-        self.graph = th.cuda.CUDAGraph()
-        state = [self.rng, env.rng if self.single else env.map_rng]
+        window = _Window()               # the generator is not registered: the selection draws from the evaluation's own `rng`
+        self.graph = window.graphs[0]
+        state = [self.rng, env.reset_rng]
         state += [m.rng_state for m in self._comm_modules() if isinstance(m.rng_state, th.Tensor)]
         if stats is not None:
-            state += list(stats.state_tensors())
+            state += stats.state_tensors()
         if film is not None:
             state.append(film.status)                # the film ROWS the warm-up wrote are overwritten by the first replay
-        snap = [t.clone() for t in state]
         # a comm module no training forward has seeded yet is seeded by the warm-up (a host round trip the capture cannot hold) and stays
         # seeded through the capture; afterwards the graph keeps ITS tensor (``_held``: the address it reads, saves and restores), the
         # module goes back to unseeded and the host generator to where it stood
         unseeded, host = self._comm_save()
-        side = th.cuda.Stream()
-        side.wait_stream(th.cuda.current_stream())
-        with th.cuda.stream(side):
-            for _ in range(max(int(warmup), 1)):     # at least once: the seeding above
-                self._body(unseed=False)
-        th.cuda.current_stream().wait_stream(side)
-        with _capture(self.graph):
-            self._body(unseed=False)
-        th.cuda.synchronize()
-        for dst, src in zip(state, snap):
-            dst.copy_(src)
+        # no learner: the evaluation writes no parameter, never draws from the generator and keeps its planes in a store of its own;
+        # at least one warm-up: the seeding above
+        _warm_up_and_capture(max(int(warmup), 1), lambda: self._body(unseed=False), window, state=state)
         self._held = [m.rng_state for m, st in unseeded if st is None and isinstance(m.rng_state, th.Tensor)]
         for t in self._held:
             t[1:].zero_()

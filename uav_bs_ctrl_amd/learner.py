@@ -322,6 +322,11 @@ class MultiAgentQLearner:
         self.apply()
         return out
 
+    def state_tensors(self) -> List[th.Tensor]:
+        """What an update moves (CUDA learner): parameters, target, Adam moments and ``hyper`` {lr, step count} - what a graph capture
+        snapshots before its warm-up and restores after the capture, and what ``state.pt`` holds of the learner."""
+        return [self.flat.flat, self.flat_target, self.optimizer.m, self.optimizer.v, self.optimizer.hyper]
+
     def needs_collective(self) -> bool:
         return bool(dist.is_available() and dist.is_initialized() and
                     (dist.get_world_size(self.group) > 1 or self.grads.force_collective))

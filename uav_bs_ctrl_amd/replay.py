@@ -34,7 +34,30 @@ class _RingState:
     ``device_state=True``: ``state`` int64 {head, size}, ``rng`` int64 {seed, draws} and ``status`` int32 [1] are DEVICE tensors; the
     commit, the sampler and the gather into a captured update's buffers are one launch each (csrc/replay.hip) that read the
     counters on the device - so a hipGraph holding them replays with the CURRENT ring position (``graphs.GraphedEpisode``).
-    A class sets ``_scheme`` (its field names) and ``mem`` / ``cur`` / ``capacity`` / ``n_envs`` / ``device`` before ``_init_ring_state``."""
+    A class sets ``_scheme`` (its field names: ``_obs_fields``, the observation side of a transition, then act / rew / done) and
+    ``mem`` / ``cur`` / ``capacity`` / ``T`` / ``n_envs`` / ``device`` before ``_init_ring_state``."""
+
+    def push(self, tr: Dict[str, th.Tensor]) -> None:
+        """One transition of every parallel env.  tr: the ``_obs_fields`` [E, ...] (observation BEFORE the action; may be absent when
+        staged), act / rew / done and the ``next_*`` observation fields (madrqn/buffer.py:18-35, drqn/buffer.py:17-29)."""
+        self.stage_obs(tr)
+        for k in ("act", "rew", "done"):
+            self.cur[k][:, self.ptr] = tr[k]
+        self.ptr += 1
+        if self.ptr == self.T:
+            for k in self._obs_fields:
+                if "next_" + k in tr:
+                    self.cur[k][:, self.T] = tr["next_" + k]
+            self._commit()
+            self.ptr = 0
+
+    def stage_obs(self, tr: Dict[str, th.Tensor]) -> None:
+        """The observation half of the current transition (the ``_obs_fields`` BEFORE the action), written at the current step
+        WITHOUT advancing: a simulator that overwrites its observation buffers in place can be stepped before ``push`` receives
+        act / rew / done / next_* - no clone of the observation in between."""
+        for k in self._obs_fields:
+            if k in tr:
+                self.cur[k][:, self.ptr] = tr[k]
 
     def _init_ring_state(self, device_state: bool, seed: Optional[int]) -> None:
         self.device_state = bool(device_state)
@@ -128,7 +151,7 @@ class _RingState:
 
 
 class SequenceReplay(_RingState):
-    _scheme = SCHEME
+    _scheme, _obs_fields = SCHEME, ("gt", "ubs", "agent", "d_u2u", "h", "state")
 
     def __init__(self, capacity: int, max_seq_len: int, n_agents: int, n_gts: int, hidden_size: int,
                  n_envs: int = 1, state_dim: int = 0, r_comm: float = float("inf"), rew_dim: Optional[int] = None,
@@ -148,32 +171,6 @@ class SequenceReplay(_RingState):
         self.mem = ring(capacity)
         self.cur = ring(n_envs)
         self._init_ring_state(device_state, seed)
-
-    def push(self, tr: Dict[str, th.Tensor]) -> None:
-        """One transition of every parallel env.  tr: gt/ubs/agent/d_u2u/h/state [E, ...] (observation BEFORE the action),
-        act [E,n], rew [E,rd], done [E,1] and the ``next_*`` observation fields (buffer.py:18-35)."""
-        t = self.ptr
-        for k in ("gt", "ubs", "agent", "d_u2u", "h", "state"):
-            if k in tr:
-                self.cur[k][:, t] = tr[k]
-        for k in ("act", "rew", "done"):
-            self.cur[k][:, t] = tr[k]
-        self.ptr += 1
-        if self.ptr == self.T:
-            for k in ("gt", "ubs", "agent", "d_u2u", "h", "state"):
-                if "next_" + k in tr:
-                    self.cur[k][:, self.T] = tr["next_" + k]
-            self._commit()
-            self.ptr = 0
-
-    def stage_obs(self, tr: Dict[str, th.Tensor]) -> None:
-        """The observation half of the current transition (gt/ubs/agent/d_u2u/h/state BEFORE the action), written at the
-        current step WITHOUT advancing: a simulator that overwrites its observation buffers in place can be stepped before
-        ``push`` receives act / rew / done / next_* - no clone of the observation in between."""
-        t = self.ptr
-        for k in ("gt", "ubs", "agent", "d_u2u", "h", "state"):
-            if k in tr:
-                self.cur[k][:, t] = tr[k]
 
     def _gather_fields(self, target, B: int):
         m, o, T = self.mem, target.obs, self.T
@@ -238,7 +235,7 @@ class SingleUbsSequenceReplay(_RingState):
     transitions, then the next observation / hidden state of the last one (buffer.py:23-25).  ``gather`` hands the learner either
     the T+1 `seen-by` batches (``from_single_ubs_obs`` on views of the gathered fields: no graph is ever stored or copied) or the
     T+1 flattened [B, 2+4M] tensors (agent || gt row-major)."""
-    _scheme = SINGLE_UBS_SCHEME
+    _scheme, _obs_fields = SINGLE_UBS_SCHEME, ("gt", "agent", "h")
 
     def __init__(self, capacity: int, max_seq_len: int, n_gts: int, hidden_size: int, n_envs: int = 1, device="cuda",
                  device_state: bool = False, seed: Optional[int] = None):
@@ -254,32 +251,6 @@ class SingleUbsSequenceReplay(_RingState):
         self.mem = ring(capacity)
         self.cur = ring(n_envs)
         self._init_ring_state(device_state, seed)
-
-    def push(self, tr: Dict[str, th.Tensor]) -> None:
-        """One transition of every parallel env.  tr: gt / agent / h [E, ...] (observation BEFORE the action; may be absent when
-        staged), act / rew / done [E,1] and next_gt / next_agent / next_h (buffer.py:17-29)."""
-        t = self.ptr
-        for k in ("gt", "agent", "h"):
-            if k in tr:
-                self.cur[k][:, t] = tr[k]
-        for k in ("act", "rew", "done"):
-            self.cur[k][:, t] = tr[k]
-        self.ptr += 1
-        if self.ptr == self.T:
-            for k in ("gt", "agent", "h"):
-                if "next_" + k in tr:
-                    self.cur[k][:, self.T] = tr["next_" + k]
-            self._commit()
-            self.ptr = 0
-
-    def stage_obs(self, tr: Dict[str, th.Tensor]) -> None:
-        """The observation half of the current transition (gt / agent / h BEFORE the action), written at the current step
-        WITHOUT advancing: the simulator overwrites its observation buffers in place, so it can be stepped before ``push``
-        receives act / rew / done / next_* - no clone of the observation in between."""
-        t = self.ptr
-        for k in ("gt", "agent", "h"):
-            if k in tr:
-                self.cur[k][:, t] = tr[k]
 
     def _gather_fields(self, target, B: int):
         m, T = self.mem, self.T

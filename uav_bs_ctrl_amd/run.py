@@ -321,7 +321,7 @@ class Run:
         import torch.distributed as dist
 
         from .film import Film
-        from .graphs import INFO_KEYS, Episode, Evaluation, GraphedEpisode, GraphedEvaluation
+        from .graphs import Episode, Evaluation, GraphedEpisode, GraphedEvaluation, info_keys
         from .learner import MultiAgentQLearner, QLearner
         from .replay import SequenceReplay, SingleUbsSequenceReplay
         from .sim import BatchedSingleUbsCoverageEnv, BatchedUbsCoverageEnv
@@ -377,7 +377,7 @@ class Run:
         graphed = bool(ours["graphed"])
         ep_cls, ev_cls = (GraphedEpisode, GraphedEvaluation) if graphed else (Episode, Evaluation)
         kw = dict(eps=(EPS_START, EPS_END, float(args.decay_steps)), updates_per_segment=int(ours["updates_per_segment"]), enc=enc)
-        self.info_keys = tuple(k for k in INFO_KEYS if not (self.single and k == "ProbCollision"))
+        self.info_keys = info_keys(self.single)
         self.stats = EpochStats(list(self.info_keys) + ["LossQ"] + ["Test" + k for k in self.info_keys], dev, cap=max(64, E, E_test))
         self.film = Film(test_env, int(args.num_test_episodes)) if self.rank == 0 else None
         # the three captures run on the fresh, empty state - also when resuming: a warm-up episode commits into the ring at the restored
@@ -479,12 +479,11 @@ class Run:
     # ---- state.pt -------------------------------------------------------------------------------------------------------------------
     def _tensors(self) -> Dict[str, object]:
         """name -> the live tensor a graph holds the address of."""
-        lr, rb, opt = self.learner, self.replay, self.learner.optimizer
-        out = {"learner.flat": lr.flat.flat, "learner.flat_target": lr.flat_target, "learner.m": opt.m, "learner.v": opt.v,
-               "learner.hyper": opt.hyper, "replay.state": rb.state, "replay.rng": rb.rng, "replay.status": rb.status,
-               "env.rng": self.env.rng if self.single else self.env.map_rng}
+        lr, rb = self.learner, self.replay
+        out = dict(zip(("learner.flat", "learner.flat_target", "learner.m", "learner.v", "learner.hyper"), lr.state_tensors()))
+        out.update({"replay.state": rb.state, "replay.rng": rb.rng, "replay.status": rb.status, "env.rng": self.env.reset_rng})
         if self.rank == 0:                       # the evaluation is rank 0's alone
-            out.update({"test_env.rng": self.test_env.rng if self.single else self.test_env.map_rng, "evaluation.rng": self.evaluation.rng})
+            out.update({"test_env.rng": self.test_env.reset_rng, "evaluation.rng": self.evaluation.rng})
         for name, ep in (("collect", self.collect), ("train", self.train_episode)):
             out.update({f"{name}.t": ep.t, f"{name}.eps": ep.eps, f"{name}.explore": ep.explore})
         out.update({"comm." + name: m.rng_state for name, m in comm_modules(lr)})

@@ -229,6 +229,11 @@ class BatchedUbsCoverageEnv:
         env.map_rng = th.tensor([int(seed), 0], dtype=th.int64, device=env.device)
         return env
 
+    @property
+    def reset_rng(self) -> Optional[th.Tensor]:
+        """The reset counter under the name both simulators share: ``map_rng``."""
+        return self.map_rng
+
     # ---- the two kernels ---------------------------------------------------------------------------------------------
     def _launch(self, actions: Optional[th.Tensor]):
         L.require_gpu(self.pos_ubs, actions)
@@ -415,6 +420,11 @@ class BatchedSingleUbsCoverageEnv:
         if seed is None:                                     # from torch's default generator: torch.manual_seed reproduces a run
             seed = int(th.randint(0, 2 ** 62, (1,)).item())
         self.rng = th.tensor([int(seed), 0], dtype=th.int64, device=dev)     # device {seed, resets} of the placement sampler
+
+    @property
+    def reset_rng(self) -> th.Tensor:
+        """The reset counter under the name both simulators share: ``rng``."""
+        return self.rng
 
     # ---- the two kernels ---------------------------------------------------------------------------------------------
     def _launch(self, actions: Optional[th.Tensor]):
