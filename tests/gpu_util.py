@@ -118,11 +118,12 @@ class _LibSpy:
         return call
 
 
-def _exp3_learner_and_sequence(B, n, M, T, dist, seed, c="tarmac", mixer=False):
+def _exp3_learner_and_sequence(B, n, M, T, dist, seed, c="tarmac", mixer=False, n_rounds=1):
     """exp3 learner whose target network differs from the policy (as it does after the first polyak step) and whose biases
     are not DGL's zeros, + one sampled batch of bench.py's generator.  c: the communication variant of run_exp3.py's grid.
     mixer: QMIX on top (embed_dim = 32, madrqn/config.py) - mixer and target mixer treated like the two networks, ``states``
-    [T + 1, B, S] of the simulator's state size in the batch, rews / dones in the team form [T, B, 1] ``_td_loss`` expands."""
+    [T + 1, B, S] of the simulator's state size in the batch, rews / dones in the team form [T, B, 1] ``_td_loss`` expands.
+    n_rounds: the communication rounds per step of CommNet / EdgeConv / TarMAC (madrqn/config.py; 1 in every exp3 launcher)."""
     import copy
 
     import bench
@@ -134,6 +135,9 @@ def _exp3_learner_and_sequence(B, n, M, T, dist, seed, c="tarmac", mixer=False):
         args = copy.copy(args)
         args.mixer, args.embed_dim = True, 32
         env_info["state_shape"] = L.lib().uavgnn_env_state_dim(n, M, 0)
+    if n_rounds != 1:
+        args = copy.copy(args)
+        args.n_rounds = n_rounds
     learner = MultiAgentQLearner(env_info, args)
     gen = th.Generator(device="cuda").manual_seed(1000 + seed)
     with th.no_grad():
