@@ -73,12 +73,12 @@ __global__ __launch_bounds__(256) void split_planes_h2_kernel(const float* __res
   const float s = pow2f(se);
   const size_t n_ih = static_cast<size_t>(3) * H * K_in, n_hh = static_cast<size_t>(3) * H * H;
   for (int i = 2 * tid; i < K_in; i += 512) {
-    const Split2 sp = split_pair(a[i] * s, a[i + 1] * s);
+    const Split2 sp = split_pair(a[i], a[i + 1], s);
     *reinterpret_cast<unsigned*>(p_ih + static_cast<size_t>(row) * K_in + i) = sp.hi;
     *reinterpret_cast<unsigned*>(p_ih + n_ih + static_cast<size_t>(row) * K_in + i) = sp.lo;
   }
   for (int i = 2 * tid; i < H; i += 512) {
-    const Split2 sp = split_pair(b[i] * s, b[i + 1] * s);
+    const Split2 sp = split_pair(b[i], b[i + 1], s);
     *reinterpret_cast<unsigned*>(p_hh + static_cast<size_t>(row) * H + i) = sp.hi;
     *reinterpret_cast<unsigned*>(p_hh + n_hh + static_cast<size_t>(row) * H + i) = sp.lo;
   }

@@ -32,27 +32,60 @@ __device__ __forceinline__ float pow2f(int e) { return __uint_as_float(static_ca
 struct Split2 {
   unsigned hi, lo;   // two packed f16 each: low half = first element
 };
-// (x, y) already scaled -> hi + lo (round to nearest even both times; x - hi is exact in fp32)
-__device__ __forceinline__ Split2 split_pair(float x, float y) {
+// The split of v at the power-of-two scale s: hi = f16(v s), lo = f16(v s - hi), round to nearest even both times, f16 subnormals kept.
+// Each term is ONE mixed-precision FMA (fp32 x fp32 + addend -> the f16 low or high half of the destination, v_fma_mixlo_f16 /
+// v_fma_mixhi_f16; lo takes hi as its f16 addend): four single-pass instructions per element pair, and no packed fp32 beside the
+// MFMAs.  Same bits as a separate multiply, conversion and subtraction: v s is exact (s is a power of two) and v s - hi is exact in
+// fp32, so the FMA's single rounding is the conversion's; the -0 addend keeps the sign of a zero product.  (Only a product below the
+// fp32 range, |v s| < 2^-150, is treated differently: there a negative one leaves lo = -0 where the rounded product gave +0; hi and
+// every dot product are the same.)  The plain C++ form compiles to five to seven VALU per pair - the compiler recomputes hi for the
+// second FMA - hence the asm; it is not volatile, so the scheduler still moves it.
+//
+// (x sx, y sy) -> hi + lo: the weight-split kernels (one pair per thread and trip)
+__device__ __forceinline__ Split2 split_pair(float x, float y, float sx, float sy) {
   Split2 s;
-  const f16x2 h = __builtin_convertvector(f32x2{x, y}, f16x2);
-  s.hi = __builtin_bit_cast(unsigned, h);
-  const f32x2 r = f32x2{x, y} - __builtin_convertvector(h, f32x2);
-  s.lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
+  const float nz = -0.f;
+  asm("v_fma_mixlo_f16 %0, %1, %2, %3" : "=v"(s.hi) : "v"(x), "v"(sx), "s"(nz));
+  asm("v_fma_mixhi_f16 %0, %1, %2, %3" : "+v"(s.hi) : "v"(y), "v"(sy), "s"(nz));
+  asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(s.lo) : "v"(x), "v"(sx), "v"(s.hi));
+  asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(s.lo) : "v"(y), "v"(sy), "v"(s.hi));
   return s;
 }
-// four consecutive k of one row (one 16-byte global load) scaled by `s` -> one 8-byte group per plane
-__device__ __forceinline__ void stage4(unsigned short* p, int plane_stride, float4 v, float s) {
-  const Split2 a = split_pair(v.x * s, v.y * s), b = split_pair(v.z * s, v.w * s);
-  *reinterpret_cast<u32x2*>(p) = u32x2{a.hi, b.hi};
-  *reinterpret_cast<u32x2*>(p + plane_stride) = u32x2{a.lo, b.lo};
+__device__ __forceinline__ Split2 split_pair(float x, float y, float s) { return split_pair(x, y, s, s); }
+// Four values (one 16-byte load) in two steps of four instructions, for the kernels that stage inside their MFMA loops: the hi words
+// {(v.x, v.y), (v.z, v.w)}, then the lo words from them.  The two destinations of a step alternate, so no instruction reads the
+// register its predecessor wrote half of (the wait state that costs), and a step is one statement: it moves as a whole and a hand
+// schedule can place it (the scheduler's instruction groups do not see asm).
+__device__ __forceinline__ u32x2 split4_hi(float4 v, float4 s) {
+  unsigned a, b;
+  const float nz = -0.f;
+  asm("v_fma_mixlo_f16 %0, %2, %6, %10\n\t"
+      "v_fma_mixlo_f16 %1, %4, %8, %10\n\t"
+      "v_fma_mixhi_f16 %0, %3, %7, %10\n\t"
+      "v_fma_mixhi_f16 %1, %5, %9, %10"
+      : "=&v"(a), "=&v"(b)
+      : "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w), "v"(s.x), "v"(s.y), "v"(s.z), "v"(s.w), "s"(nz));
+  return u32x2{a, b};
 }
-// four consecutive columns of one row, each with its own column scale -> one 8-byte group per plane
+__device__ __forceinline__ u32x2 split4_lo(float4 v, float4 s, u32x2 hi) {
+  unsigned a, b;
+  asm("v_fma_mixlo_f16 %0, %2, %6, -%10 op_sel_hi:[0,0,1]\n\t"
+      "v_fma_mixlo_f16 %1, %4, %8, -%11 op_sel_hi:[0,0,1]\n\t"
+      "v_fma_mixhi_f16 %0, %3, %7, -%10 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
+      "v_fma_mixhi_f16 %1, %5, %9, -%11 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
+      : "=&v"(a), "=&v"(b)
+      : "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w), "v"(s.x), "v"(s.y), "v"(s.z), "v"(s.w), "v"(hi[0]), "v"(hi[1]));
+  return u32x2{a, b};
+}
+__device__ __forceinline__ float4 scale4(float s) { return make_float4(s, s, s, s); }
+// four consecutive columns of one row, each at its own column scale -> one 8-byte group per plane
 __device__ __forceinline__ void stage4(unsigned short* p, int plane_stride, float4 v, float4 s) {
-  const Split2 a = split_pair(v.x * s.x, v.y * s.y), b = split_pair(v.z * s.z, v.w * s.w);
-  *reinterpret_cast<u32x2*>(p) = u32x2{a.hi, b.hi};
-  *reinterpret_cast<u32x2*>(p + plane_stride) = u32x2{a.lo, b.lo};
+  const u32x2 hi = split4_hi(v, s);
+  *reinterpret_cast<u32x2*>(p) = hi;
+  *reinterpret_cast<u32x2*>(p + plane_stride) = split4_lo(v, s, hi);
 }
+// four consecutive k of one row (one 16-byte global load) at the row's scale `s` -> one 8-byte group per plane
+__device__ __forceinline__ void stage4(unsigned short* p, int plane_stride, float4 v, float s) { stage4(p, plane_stride, v, scale4(s)); }
 
 }  // namespace h2
 }  // namespace uavgnn

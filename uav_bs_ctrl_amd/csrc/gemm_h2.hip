@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void split_h2_kernel(const float* __restrict__
   const int se = scale_exp(m);
   const float s = pow2f(se);
   for (int j = 2 * tid; j < ocol_n; j += 512) {
-    const Split2 sp = split_pair(at(j) * s, at(j + 1) * s);
+    const Split2 sp = split_pair(at(j), at(j + 1), s);
     *reinterpret_cast<unsigned*>(planes + static_cast<size_t>(orow) * ocol_n + j) = sp.hi;
     *reinterpret_cast<unsigned*>(planes + n + static_cast<size_t>(orow) * ocol_n + j) = sp.lo;
   }
@@ -166,6 +166,11 @@ __global__ __launch_bounds__(NT) void gemm_nt_h2w8_kernel(const float* __restric
     unsigned short* sa = reinterpret_cast<unsigned short*>(smem + buf * BUF) + sa_w;
     stage4(sa + 64 * i * 32, PA * 8, ra[i], sca[i]);
   };
+  auto lstore_a_planes = [&](int buf, int i, u32x2 hi, u32x2 lo) {   // stage4's two stores, for the loop that places the split's steps itself
+    unsigned short* sa = reinterpret_cast<unsigned short*>(smem + buf * BUF) + sa_w + 64 * i * 32;
+    *reinterpret_cast<u32x2*>(sa) = hi;
+    *reinterpret_cast<u32x2*>(sa + PA * 8) = lo;
+  };
   auto lstore_b = [&](int buf) {
     u32x4* sb = smem + buf * BUF;
 #pragma unroll
@@ -219,24 +224,25 @@ __global__ __launch_bounds__(NT) void gemm_nt_h2w8_kernel(const float* __restric
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
+      // The split steps are asm, which the scheduler's instruction groups do not see: the eight MFMAs of the two remaining terms take
+      // one step each (four single-pass instructions in a 32-cycle gap), row i's stores ride with the next row's first step, and each
+      // MFMA with its share is a region of its own.  The loads of slice t + 2 follow the last step, which frees their registers.
+      u32x2 sh[4], sl[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) lstore_a((t + 1) & 1, i);
-      UAVGNN_H2_TERM(1, 0)
-#pragma unroll
-      for (int sg = 0; sg < 4; ++sg) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 12, 0);
-        __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);
+      for (int g = 0; g < 8; ++g) {
+        const int i = g >> 1;
+        if (g < 4) acc[g >> 1][g & 1] = mfma32(F.a[g >> 1][1], F.b[g & 1][0], acc[g >> 1][g & 1]);
+        else acc[(g - 4) >> 1][g & 1] = mfma32(F.a[(g - 4) >> 1][0], F.b[g & 1][0], acc[(g - 4) >> 1][g & 1]);
+        if ((g & 1) == 0) {
+          if (i > 0) lstore_a_planes((t + 1) & 1, i - 1, sh[i - 1], sl[i - 1]);
+          sh[i] = split4_hi(ra[i], scale4(sca[i]));
+        } else {
+          sl[i] = split4_lo(ra[i], scale4(sca[i]), sh[i]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
       }
-      __builtin_amdgcn_sched_barrier(0);
+      lstore_a_planes((t + 1) & 1, 3, sh[3], sl[3]);
       gload_a(tn);
-      UAVGNN_H2_TERM(0, 0)
-#pragma unroll
-      for (int sg = 0; sg < 4; ++sg) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-      }
       __builtin_amdgcn_sched_barrier(0);
       __syncthreads();
       UAVGNN_H2_READ(f0, (t + 1) & 1, 0)

@@ -29,8 +29,9 @@
 //
 // Kernel structure: gru_x3.hip's (512 threads = 128 agents x 64 hidden units, eight wavefronts of 32 x 32 x 4 accumulator sets on
 // v_mfma_f32_32x32x16_f16, double-buffered LDS planes with one barrier per 32-wide K slice, staging interleaved with the first MFMA
-// group) with two planes instead of three: 40 KB per LDS stage instead of 60, 8 fragment reads per slice half instead of 12, 3 VALU per
-// staged element instead of 5.5 (v_pk_mul, v_cvt_pk_f16_f32, v_cvt_f32_f16, v_pk_fma, v_cvt_pk_f16_f32).
+// group) with two planes instead of three: 40 KB per LDS stage instead of 60, 8 fragment reads per slice half instead of 12, 2 VALU per
+// staged element instead of 5.5 (four mixed-precision FMAs per element pair: csrc/f16x2.h).  The file is compiled without packed fp32
+// (uav_bs_ctrl_amd/build.py): the epilogue's un-scaling stays single-pass fp32 beside the MFMAs of the other wavefronts.
 #include <type_traits>
 
 #include "common.h"
@@ -66,12 +67,12 @@ __global__ __launch_bounds__(256) void split_planes_h2_kernel(const float* __res
   const float s = pow2f(se);
   const size_t n_ih = static_cast<size_t>(3) * H * K_in, n_hh = static_cast<size_t>(3) * H * H;
   for (int i = 2 * tid; i < K_in; i += 512) {
-    const Split2 sp = split_pair(a[i] * s, a[i + 1] * s);
+    const Split2 sp = split_pair(a[i], a[i + 1], s);
     *reinterpret_cast<unsigned*>(p_ih + static_cast<size_t>(row) * K_in + i) = sp.hi;
     *reinterpret_cast<unsigned*>(p_ih + n_ih + static_cast<size_t>(row) * K_in + i) = sp.lo;
   }
   for (int i = 2 * tid; i < H; i += 512) {
-    const Split2 sp = split_pair(b[i] * s, b[i + 1] * s);
+    const Split2 sp = split_pair(b[i], b[i + 1], s);
     *reinterpret_cast<unsigned*>(p_hh + static_cast<size_t>(row) * H + i) = sp.hi;
     *reinterpret_cast<unsigned*>(p_hh + n_hh + static_cast<size_t>(row) * H + i) = sp.lo;
   }
@@ -176,10 +177,17 @@ __global__ __launch_bounds__(NT) void gru_cell_fwd_h2_kernel(
 #pragma unroll
     for (int i = 0; i < 3; ++i) sb[sbw[i]] = rw[S][i];
   };
+  // staging of A row i in three parts (the split's two steps, then the two 8-byte stores), so that the loop can place them one by one
+  auto split_a_hi = [&](int i, auto set) { return split4_hi(ra[decltype(set)::value][i], scale4(sca[i])); };
+  auto split_a_lo = [&](int i, auto set, u32x2 hi) { return split4_lo(ra[decltype(set)::value][i], scale4(sca[i]), hi); };
+  auto lstore_a_planes = [&](int buf, int i, u32x2 hi, u32x2 lo) {
+    unsigned short* sa = reinterpret_cast<unsigned short*>(smem + buf * BUF) + sa_w + 64 * i * 32;
+    *reinterpret_cast<u32x2*>(sa) = hi;
+    *reinterpret_cast<u32x2*>(sa + PA * 8) = lo;
+  };
   auto lstore_a = [&](int buf, int i, auto set) {
-    constexpr int S = decltype(set)::value;
-    unsigned short* sa = reinterpret_cast<unsigned short*>(smem + buf * BUF) + sa_w;
-    stage4(sa + 64 * i * 32, PA * 8, ra[S][i], sca[i]);
+    const u32x2 hi = split_a_hi(i, set);
+    lstore_a_planes(buf, i, hi, split_a_lo(i, set, hi));
   };
   auto lstore = [&](int buf, auto set) {
     lstore_a(buf, 0, set);
@@ -201,12 +209,9 @@ __global__ __launch_bounds__(NT) void gru_cell_fwd_h2_kernel(
     _Pragma("unroll") for (int gate = 0; gate < 3; ++gate) _Pragma("unroll") for (int pl = 0; pl < 2; ++pl)        \
         F.b[gate][pl] = as_frag(sb[2 * PA + pl * PB + (gate * BJ + wc + l32) * 4 + ((2 * (kh) + lh) ^ sw)]);       \
   }
-#define UAVGNN_H2_TERM(ia, ib)                       \
-  if (!(UAVGNN_H2_DBG_ & 8)) {                       \
-    acc[0] = mfma32(F.a[ia], F.b[0][ib], acc[0]);    \
-    acc[1] = mfma32(F.a[ia], F.b[1][ib], acc[1]);    \
-    acc[NSET] = mfma32(F.a[ia], F.b[2][ib], acc[NSET]); \
-  }
+#define UAVGNN_H2_ONE(gate, set, ia, ib) \
+  if (!(UAVGNN_H2_DBG_ & 8)) acc[set] = mfma32(F.a[ia], F.b[gate][ib], acc[set]);
+#define UAVGNN_H2_TERM(ia, ib) UAVGNN_H2_ONE(0, 0, ia, ib) UAVGNN_H2_ONE(1, 1, ia, ib) UAVGNN_H2_ONE(2, NSET, ia, ib)
 #define UAVGNN_H2_MFMA(F_, NSET_)                                  \
   {                                                                \
     constexpr int NSET = NSET_;                                    \
@@ -243,21 +248,26 @@ __global__ __launch_bounds__(NT) void gru_cell_fwd_h2_kernel(
       __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   \
     }                                                      \
     __builtin_amdgcn_sched_barrier(0);                     \
-    if (!(UAVGNN_H2_DBG & 2)) { lstore_a((t + 1) & 1, 0, SET_{}); lstore_a((t + 1) & 1, 1, SET_{}); } \
-    UAVGNN_H2_TERM(1, 0)                                   \
-    _Pragma("unroll") for (int sg = 0; sg < 3; ++sg) {     \
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   \
-      __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);   \
-      __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);   \
-    }                                                      \
+    /* the split steps are asm, which the scheduler's instruction groups do not see: one step or one row's stores per MFMA, */ \
+    /* each in a region of its own (four single-pass instructions and at most two LDS writes in a 32-cycle MFMA gap)        */ \
+    u32x2 sh0, sl0, sh1, sl1;                              \
+    UAVGNN_H2_ONE(0, 0, 1, 0)                              \
+    if (!(UAVGNN_H2_DBG & 2)) sh0 = split_a_hi(0, SET_{}); \
     __builtin_amdgcn_sched_barrier(0);                     \
+    UAVGNN_H2_ONE(1, 1, 1, 0)                              \
+    if (!(UAVGNN_H2_DBG & 2)) sl0 = split_a_lo(0, SET_{}, sh0); \
+    __builtin_amdgcn_sched_barrier(0);                     \
+    UAVGNN_H2_ONE(2, NSET, 1, 0)                           \
+    if (!(UAVGNN_H2_DBG & 2)) { lstore_a_planes((t + 1) & 1, 0, sh0, sl0); sh1 = split_a_hi(1, SET_{}); } \
+    __builtin_amdgcn_sched_barrier(0);                     \
+    UAVGNN_H2_ONE(0, 0, 0, 0)                              \
+    if (!(UAVGNN_H2_DBG & 2)) sl1 = split_a_lo(1, SET_{}, sh1); \
+    __builtin_amdgcn_sched_barrier(0);                     \
+    UAVGNN_H2_ONE(1, 1, 0, 0)                              \
+    if (!(UAVGNN_H2_DBG & 2)) lstore_a_planes((t + 1) & 1, 1, sh1, sl1); \
     if (!(UAVGNN_H2_DBG & 1)) gload_a(SET_{});             \
-    UAVGNN_H2_TERM(0, 0)                                   \
-    _Pragma("unroll") for (int sg = 0; sg < 3; ++sg) {     \
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   \
-      __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);   \
-      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   \
-    }                                                      \
+    __builtin_amdgcn_sched_barrier(0);                     \
+    UAVGNN_H2_ONE(2, NSET, 0, 0)                           \
     __builtin_amdgcn_sched_barrier(0);                     \
     if (!(UAVGNN_H2_DBG & 1)) advance();                   \
   }                                                        \
@@ -292,6 +302,7 @@ __global__ __launch_bounds__(NT) void gru_cell_fwd_h2_kernel(
 #undef UAVGNN_H2_MFMA
 #undef UAVGNN_H2_READ
 #undef UAVGNN_H2_TERM
+#undef UAVGNN_H2_ONE
   __syncthreads();   // the last iteration's read of the stale buffer must not race the epilogue's tile
   // ---- epilogue on the D layout: lane l holds column l % 32, register i holds row 8 (i / 4) + 4 (l / 32) + i % 4 ----------------
   float* sH = reinterpret_cast<float*>(smem);             // [128][ST] fp32 tile: h in, h' out, 16-byte row-contiguous HBM accesses
