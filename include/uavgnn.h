@@ -711,6 +711,16 @@ int uavgnn_gemm_tn_h2_supported(long long n_rows, int Mo, int Ko);
 int uavgnn_gemm_tn_h2_chunks(long long n_rows, int Mo, int Ko);
 int uavgnn_gemm_tn_h2(const float* dY, long long ldy, int Mo, const float* X, long long ldx, int Ko, long long n_rows,
                       const float* colmax_y, const float* colmax_x, float* partials, int S, int accumulate, uavgnn_stream_t stream);
+/* Output tiles are 256 rows by tj columns, tj = uavgnn_gemm_tn_h2_width(Ko): 160 where 160 divides Ko and 128 does not (dW_ih, Ko = 320),
+ * else 96 where 96 divides Ko and neither 128 nor 160 does (dWp^T, Ko = 96), else 128 - no column tile of MFMAs is padding where such a
+ * width exists.  uavgnn_gemm_tn_h2_chunks counts tiles at that width.  The _tj forms take the width as an argument (96, 128 or 160; 0 = the
+ * rule; anything else UAVGNN_EINVAL / 0 chunks): every width takes every Ko, and a partial product P[s] does not depend on the width, bit
+ * for bit - only the default chunk count S does (and with it where the fixed-order sum over the rows is cut). */
+int uavgnn_gemm_tn_h2_width(int Ko);
+int uavgnn_gemm_tn_h2_chunks_tj(long long n_rows, int Mo, int Ko, int tj);
+int uavgnn_gemm_tn_h2_tj(const float* dY, long long ldy, int Mo, const float* X, long long ldx, int Ko, long long n_rows,
+                         const float* colmax_y, const float* colmax_x, float* partials, int S, int accumulate, int tj,
+                         uavgnn_stream_t stream);
 int uavgnn_gru_gates_bwd_fused(const float* pre, const float* h, const float* d_hout, int N, int H, float* d_gi, float* d_gh,
                                float* d_h, uavgnn_stream_t stream);
 /* The same with the Q head's input gradient folded in: the gradient of h' is d_hout (NULL = 0) + dq W_out, dq [N, n_out] the

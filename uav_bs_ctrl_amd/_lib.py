@@ -121,6 +121,10 @@ SIGNATURES = {
     "uavgnn_gemm_tn_h2_chunks": (_c_int, [ctypes.c_longlong, _c_int, _c_int]),
     "uavgnn_gemm_tn_h2": (_c_int, [_c_fp, ctypes.c_longlong, _c_int, _c_fp, ctypes.c_longlong, _c_int, ctypes.c_longlong, _c_fp, _c_fp, _c_fp,
                                    _c_int, _c_int, _c_st]),
+    "uavgnn_gemm_tn_h2_width": (_c_int, [_c_int]),
+    "uavgnn_gemm_tn_h2_chunks_tj": (_c_int, [ctypes.c_longlong, _c_int, _c_int, _c_int]),
+    "uavgnn_gemm_tn_h2_tj": (_c_int, [_c_fp, ctypes.c_longlong, _c_int, _c_fp, ctypes.c_longlong, _c_int, ctypes.c_longlong, _c_fp, _c_fp, _c_fp,
+                                      _c_int, _c_int, _c_int, _c_st]),
     "uavgnn_gemm_h2_supported": (_c_int, [_c_int, _c_int, _c_int]),
     "uavgnn_split_h2_bytes": (ctypes.c_longlong, [_c_int, _c_int]),
     "uavgnn_split_h2": (_c_int, [_c_fp, _c_int, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_st]),

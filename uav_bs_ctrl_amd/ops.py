@@ -707,8 +707,12 @@ GRU_X3_FLAGS = 1 if os.environ.get("UAVGNN_GRU_X3_VARIANT", "1") == "0" else 0
 GEMM_X3_SMALL_GRID = 128   # fewer 256 x 128 tiles than this: 128 x 128 tiles instead
 
 
+GEMM_X3_MIN_ROWS = 4096   # fewer rows: the vendor GEMM
+
+
 def gemm_x3_supported(a, n_out, k) -> bool:
-    return bool(GEMM_X3 and a.is_cuda and a.dtype == th.float32 and a.dim() == 2 and _mc_operand(a) and n_out % 128 == 0 and a.shape[0] >= 4096
+    return bool(GEMM_X3 and a.is_cuda and a.dtype == th.float32 and a.dim() == 2 and _mc_operand(a) and n_out % 128 == 0
+                and a.shape[0] >= GEMM_X3_MIN_ROWS
                 and a.shape[0] * a.stride(0) < 2 ** 31 and L.lib().uavgnn_gemm_x3_supported(a.shape[0], n_out, k))
 
 
@@ -892,6 +896,9 @@ GEMM_TN_MIN_ROWS = 1 << 18
 # ... on the f16x2 arithmetic with LDS transposing reads (csrc/gemm_tn_h2.hip): the recurrent weights of a staged BPTT sequence
 # (A/B switch: bench.py's result line names UAVGNN_GEMM_TN_H2=0 as the way back to bf16x3 / the vendor GEMM)
 GEMM_TN_H2 = os.environ.get("UAVGNN_GEMM_TN_H2", "1") != "0"
+# ... on 256 x 160 / 256 x 96 output tiles where such a width divides the input width and 128 does not (dW_ih, dWp: no padded MFMA column
+# tile; uavgnn_gemm_tn_h2_width).  A/B switch: UAVGNN_GEMM_TN_TILES=0 runs every product on the 128-wide tiles at their chunk count
+GEMM_TN_TILES = os.environ.get("UAVGNN_GEMM_TN_TILES", "1") != "0"
 
 
 def _max_two_stage(t):
@@ -954,7 +961,8 @@ def _wgrad_partials(dy, x, bounds=None, allow_tn=True, slot=None):
     sink's slots; tag: "tnh2", "tn" or None for the vendor product); default: a fresh buffer."""
     n, Mo, Ko = dy.shape[0], dy.shape[1], x.shape[1]
     if bounds is not None:
-        tag, S = "tnh2", L.lib().uavgnn_gemm_tn_h2_chunks(n, Mo, Ko)
+        tag = "tnh2"
+        S = L.lib().uavgnn_gemm_tn_h2_chunks(n, Mo, Ko) if GEMM_TN_TILES else L.lib().uavgnn_gemm_tn_h2_chunks_tj(n, Mo, Ko, 128)
     elif allow_tn and gemm_tn_x3_supported(dy, x):      # (is_cuda first: the sink's host tests run on CPU tensors, without the library)
         tag, S = "tn", L.lib().uavgnn_gemm_tn_x3_chunks(n, Mo, Ko)
     else:
@@ -965,8 +973,10 @@ def _wgrad_partials(dy, x, bounds=None, allow_tn=True, slot=None):
     if tag == "tnh2":
         cy, cx = bounds[0].expand(Mo).contiguous(), bounds[1].expand(Ko).contiguous()
         with KERNEL_TIMER.span("gemm_tn_h2", (n, Mo, Ko)):
-            rc = L.lib().uavgnn_gemm_tn_h2(dy.data_ptr(), dy.stride(0), Mo, x.data_ptr(), x.stride(0), Ko, n, cy.data_ptr(), cx.data_ptr(),
-                                           part.data_ptr(), S, int(accumulate), L.stream())
+            args = (dy.data_ptr(), dy.stride(0), Mo, x.data_ptr(), x.stride(0), Ko, n, cy.data_ptr(), cx.data_ptr(), part.data_ptr(), S,
+                    int(accumulate))
+            rc = (L.lib().uavgnn_gemm_tn_h2(*args, L.stream()) if GEMM_TN_TILES
+                  else L.lib().uavgnn_gemm_tn_h2_tj(*args, 128, L.stream()))
         L.check(rc, "uavgnn_gemm_tn_h2")
     elif tag == "tn":
         gemm_tn_x3(dy, x, part, accumulate)
