@@ -4,7 +4,10 @@ uavgnn_gemm_nt_h2_rm2 with its row maxima, uavgnn_gemm_nt_h2_n64, uavgnn_gemm_tn
 uavgnn_gru_cell_fwd_h2 (no-grad and training with every saved set) on the seeded operands of tools/record_f16x2_golden.py, whose
 magnitudes reach 2^-30 of their row / column bound (lo terms and f16 subnormals in the in-loop staging).  The fixtures under
 tests/golden/f16x2_mix/ were written by that tool on the earlier build; per output they hold the SHA-256 of the whole int32 image and
-the image itself (whole up to 64 KB, every fourth row and the last two beyond)."""
+the image itself (whole up to 64 KB, every fourth row and the last two beyond).
+A recording pins bits, right or wrong.  That the ragged shapes pinned here are RIGHT - the clamped row of M = 257, the partial column
+block of N = 192, the second source's first slice at K1 = 32 of K = 64, the n64 kernel at M = 129, the cell at N = 129 with a two-piece
+input - is checked against float64, entry by entry, in tests/test_f16x2_nt_edges_gpu.py and tests/test_gru_cell_h2_edges_gpu.py."""
 import os
 import sys
 

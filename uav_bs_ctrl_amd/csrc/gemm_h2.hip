@@ -27,6 +27,11 @@ constexpr int BN = 128, BK = 32, BM8 = 256, NT = 512;
 constexpr int PA = BM8 * 4, PB = BN * 4;               // 16-byte chunks per split plane of the X / B tile
 constexpr int BUF = 2 * PA + 2 * PB;                   // chunks per buffer (48 KB)
 
+// The epilogue's ReLU.  fmaxf(NaN, 0) is 0: the plain maximum turned every output of a row that holds Inf / NaN, or whose bound is too
+// small, into 0 - a plausible number, against the contract of gru_h2.hip's header (tests/test_f16x2_nt_edges_gpu.py::test_contract_rows).
+// A NaN passes; every number gets fmaxf's bits.
+__device__ __forceinline__ float relu_keep_nan(float v) { return v != v ? v : fmaxf(v, 0.f); }
+
 // W [R, C] (row stride ld) -> planes [2][R][C] (transpose: [2][C][R]) + winv[rows of the output] = 2^-e: one workgroup per output row
 __global__ __launch_bounds__(256) void split_h2_kernel(const float* __restrict__ W, int ld, int R, int C, int transpose,
                                                        unsigned short* __restrict__ planes, float* __restrict__ winv) {
@@ -310,7 +315,7 @@ __global__ __launch_bounds__(NT) void gemm_nt_h2w8_kernel(const float* __restric
       const float4 t = *reinterpret_cast<const float4*>(sT + row * LDT + 4 * cc);
       float4 o = t;
       if constexpr (ACC) o = {yv[q].x + t.x, yv[q].y + t.y, yv[q].z + t.z, yv[q].w + t.w};
-      if (RELU) o = {fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f)};
+      if (RELU) o = {relu_keep_nan(o.x), relu_keep_nan(o.y), relu_keep_nan(o.z), relu_keep_nan(o.w)};
       if (m0 + row < M) *reinterpret_cast<float4*>(Y + static_cast<size_t>(m0 + row) * ldy + n0 + 4 * cc) = o;
     }
     return;
@@ -331,7 +336,7 @@ __global__ __launch_bounds__(NT) void gemm_nt_h2w8_kernel(const float* __restric
           float* p = Y + static_cast<size_t>(row) * ldy + col;
           float v = acc[a][b][i] * ci * sInv[lrow] + bv;
           if (ACC) v += *p;
-          if (RELU) v = fmaxf(v, 0.f);
+          if (RELU) v = relu_keep_nan(v);
           *p = v;
         }
       }
