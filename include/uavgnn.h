@@ -306,6 +306,15 @@ int uavgnn_film_click_subs(int B, int M, int T, int A, double dt, int episodes, 
  *   Slot s is keyed by the first word of Philox4x32-10 at counter (s, 0, draws) and key seed; the B smallest (key, slot) pairs
  *   are taken (the rule is spelled out in csrc/replay.hip).  The result depends on (seed, draws, size, B) only.  size < B:
  *   status |= 1 and idx[i] = i % max(size, 1).  capacity <= 65536, else UAVGNN_EUNSUPPORTED.
+ * _sample_wide (csrc/replay_wide.hip): the same draw - the same rule, so the same bits as _sample wherever both apply - for every
+ *   capacity in [1, 2^30] (above: UAVGNN_EUNSUPPORTED; null pointers, negative sizes, a workspace that is not 16-byte aligned:
+ *   UAVGNN_EINVAL).  One workgroup per _slots_per_workgroup() slots of the CAPACITY; seven launches (zero, four key-byte histograms,
+ *   count, write) whose number and grids depend on capacity and B alone, never on the device-side size, ordered by the stream; integer
+ *   arithmetic and 32-bit integer atomics only, so the result is the same bits run to run.  Workgroups whose chunk lies beyond size do
+ *   nothing.  workspace: DEVICE memory of _workspace_bytes(capacity) bytes (<= 0: capacity < 1 or above the limit; 8.2 KB + 8 B per
+ *   workgroup), owned by the caller at a fixed address; the call does not depend on its contents at entry (its first launch writes what
+ *   the later ones read) and carries nothing to the next draw.  rng[1] is advanced once, by one thread of the last launch; status is
+ *   only OR-ed; idx[0 .. B) is written and nothing else.  B == 0: draws += 1, nothing written.
  * _gather: one launch moves every field of the B sampled sequences into time-major buffers: slab_bytes bytes at
  *   src + idx[b] src_seq_stride + t slab_bytes -> dst + t dst_step_stride + b slab_bytes for t < steps.  fields: HOST int64
  *   [n_fields, 7] = {source base, destination base, slab_bytes, steps, src_seq_stride, dst_step_stride, sequences in the ring};
@@ -313,6 +322,10 @@ int uavgnn_film_click_subs(int B, int M, int T, int A, double dt, int episodes, 
 int uavgnn_replay_commit(const long long* fields, int n_fields, int E, int capacity, long long* state, uavgnn_stream_t stream);
 int uavgnn_replay_sample(const long long* state, long long* rng, int capacity, int B, long long* idx, int32_t* status,
                          uavgnn_stream_t stream);
+long long uavgnn_replay_sample_wide_workspace_bytes(int capacity);   /* host only */
+int uavgnn_replay_sample_wide_slots_per_workgroup(void);             /* host only */
+int uavgnn_replay_sample_wide(const long long* state, long long* rng, int capacity, int B, long long* idx, int32_t* status,
+                              void* workspace, uavgnn_stream_t stream);
 int uavgnn_replay_gather(const long long* fields, int n_fields, const long long* idx, int B, uavgnn_stream_t stream);
 
 /* ---- bias gradients ---------------------------------------------------------------------------------------------

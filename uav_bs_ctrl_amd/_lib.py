@@ -99,6 +99,9 @@ SIGNATURES = {
     "uavgnn_film_click_subs": (_c_int, [_c_int] * 4 + [ctypes.c_double, _c_int, _c_int] + [_c_fp] * 17 + [_c_st]),
     "uavgnn_replay_commit": (_c_int, [ctypes.POINTER(ctypes.c_longlong), _c_int, _c_int, _c_int, ctypes.c_void_p, _c_st]),
     "uavgnn_replay_sample": (_c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_int, _c_int, ctypes.c_void_p, _c_ip, _c_st]),
+    "uavgnn_replay_sample_wide_workspace_bytes": (ctypes.c_longlong, [_c_int]),
+    "uavgnn_replay_sample_wide_slots_per_workgroup": (_c_int, []),
+    "uavgnn_replay_sample_wide": (_c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_int, _c_int, ctypes.c_void_p, _c_ip, ctypes.c_void_p, _c_st]),
     "uavgnn_replay_gather": (_c_int, [ctypes.POINTER(ctypes.c_longlong), _c_int, ctypes.c_void_p, _c_int, _c_st]),
     "uavgnn_colsum_acc": (_c_int, [_c_fp, ctypes.c_longlong, _c_int, _c_int, _c_fp, _c_int, _c_st]),
     "uavgnn_qmix_mix_fwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_fp, _c_st]),

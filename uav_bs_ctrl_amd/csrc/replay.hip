@@ -27,6 +27,9 @@
 // over contiguous slot chunks.  Keys are recomputed per pass (64 Philox calls per thread and pass at 65 536 slots) instead of
 // held: 65 536 keys do not fit the LDS of one workgroup.  capacity <= 65536, else UAVGNN_EUNSUPPORTED.
 //   size < B: status |= 1 and idx[i] = i % max(size, 1) - nothing downstream can read outside the ring; draws += 1 all the same.
+// Which entry point serves which ring: uavgnn_replay_sample (here) every capacity <= 65 536 - the rings of every run so far, which keep
+// their one launch; uavgnn_replay_sample_wide (csrc/replay_wide.hip) every capacity in [1, 2^30] under the SAME RULE, so the same bits
+// wherever both apply, in seven launches over one workgroup per 4096 slots; replay.py picks by capacity (> 65 536: the wide one).
 //
 // uavgnn_replay_gather.  One launch moves every field of the B sampled sequences from the ring into the TIME-MAJOR fixed-address
 // buffers of a captured update: for field f, sampled row b and step t < steps,
@@ -41,6 +44,7 @@
 // double WITHOUT contraction (each of the division, the product and the difference rounded on its own - run.py:61's
 // -(eps_start - eps_end) / decay_steps * t + eps_start gives the same bits, negation being exact), then t += inc.
 #include "common.h"
+#include "replay_sample.h"
 
 namespace uavgnn {
 namespace {
@@ -142,25 +146,7 @@ __global__ __launch_bounds__(kCopyThreads) void replay_gather_kernel(GatherArgs 
   else gather_words<uint32_t>(f, src, dst, first, stride);
 }
 
-// ---- the sampler ----------------------------------------------------------------------------------------------------------
-struct SampleKey {
-  uint32_t d0, d1, k0, k1;
-  __device__ __forceinline__ uint32_t operator()(uint32_t s) const {
-    uint32_t c[4] = {s, 0u, d0, d1};
-    philox4x32_10(c, k0, k1);
-    return c[0];
-  }
-};
-
-__device__ __forceinline__ int wave_inclusive_scan(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    const int up = __shfl_up(v, o);
-    v += lane >= o ? up : 0;
-  }
-  return v;
-}
-
+// ---- the sampler (SampleKey, wave_inclusive_scan: replay_sample.h) ----------------------------------------------------------
 __global__ __launch_bounds__(kSampleThreads) void replay_sample_kernel(const long long* __restrict__ state,
                                                                        long long* __restrict__ rng, int capacity, int B,
                                                                        long long* __restrict__ idx, int* __restrict__ status) {

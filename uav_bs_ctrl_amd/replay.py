@@ -27,6 +27,8 @@ from . import _lib as L
 from .graph import HeteroBatch, from_obs_dicts, from_padded_obs, from_padded_obs_flat, from_single_ubs_obs, batch as hb_batch
 
 SCHEME = ("gt", "ubs", "agent", "d_u2u", "h", "state", "act", "rew", "done")
+NARROW_SAMPLER_CAPACITY = 65536      # uavgnn_replay_sample: one workgroup, one launch; above it uavgnn_replay_sample_wide
+MAX_DEVICE_CAPACITY = 2 ** 30        # the limit of uavgnn_replay_sample_wide
 
 
 class _RingState:
@@ -59,6 +61,18 @@ class _RingState:
             if k in tr:
                 self.cur[k][:, self.ptr] = tr[k]
 
+    def _check_device_state(self, device_state: bool) -> None:
+        """What ``device_state=True`` asks of ``device`` / ``n_envs`` / ``capacity`` - a constructor calls it BEFORE it allocates the ring."""
+        if not device_state:
+            return
+        if self.device.type != "cuda":
+            raise ValueError("device_state=True: the ring counters and the sampler live on the GPU (no CPU fallback exists)")
+        if self.n_envs > self.capacity:
+            raise ValueError(f"device_state=True: one commit of n_envs = {self.n_envs} sequences exceeds capacity = {self.capacity}")
+        if self.capacity > MAX_DEVICE_CAPACITY:
+            raise ValueError(f"device_state=True: capacity = {self.capacity} exceeds the device sampler's limit of 2^30 = "
+                             f"{MAX_DEVICE_CAPACITY} sequences")
+
     def _init_ring_state(self, device_state: bool, seed: Optional[int]) -> None:
         self.device_state = bool(device_state)
         self.ptr = 0            # time index inside the sequences under construction (buffer.py:16)
@@ -68,16 +82,18 @@ class _RingState:
             if seed is not None:
                 raise ValueError("seed: the key of the device sampler (device_state=True); the host sampler takes generator=")
             return
-        if self.device.type != "cuda":
-            raise ValueError("device_state=True: the ring counters and the sampler live on the GPU (no CPU fallback exists)")
-        if self.n_envs > self.capacity:
-            raise ValueError(f"device_state=True: one commit of n_envs = {self.n_envs} sequences exceeds capacity = {self.capacity}")
-        if seed is None:        # from torch's default generator: torch.manual_seed reproduces a run
+        self._check_device_state(True)
+        if seed is None:       # from torch's default generator: torch.manual_seed reproduces a run
             seed = int(th.randint(0, 2 ** 62, (1,)).item())
         self.head = self.size = None                          # the counters are ``state`` on the device
         self.state = th.zeros(2, dtype=th.int64, device=self.device)
         self.rng = th.tensor([int(seed), 0], dtype=th.int64, device=self.device)
         self.status = th.zeros(1, dtype=th.int32, device=self.device)
+        # capacity > 65 536: the many-workgroup sampler and its scratch (fixed address: a captured draw replays on it; nothing in it
+        # outlives a draw, so neither state.pt nor a resumed run knows it).  Up to 65 536 the one-launch sampler, as before.
+        self._sample_ws = None
+        if self.capacity > NARROW_SAMPLER_CAPACITY:
+            self._sample_ws = th.empty(L.lib().uavgnn_replay_sample_wide_workspace_bytes(self.capacity), dtype=th.uint8, device=self.device)
         rows = []
         for k in self._scheme:
             src, dst = self.cur[k], self.mem[k]
@@ -105,11 +121,17 @@ class _RingState:
     def sample_indices(self, batch_size: int, generator: Optional[th.Generator] = None) -> th.Tensor:
         """Without replacement, like ``random.sample`` (buffer.py:37-39).  device_state=True: one sampler launch keyed by the device
         ``rng`` pair - a uniform subset in ASCENDING slot order (``random.sample`` returns a random order; the loss is a mean over
-        the batch) - no host synchronisation: asking for more than the ring holds sets ``status`` (``check()``)."""
+        the batch) - no host synchronisation: asking for more than the ring holds sets ``status`` (``check()``).
+        capacity > 65 536: the same draw, bit for bit, from the many-workgroup sampler (seven launches, csrc/replay_wide.hip)."""
         if self.device_state:
             if generator is not None:
                 raise ValueError("device_state=True: the sampler is keyed by the device `rng` pair, not by a torch generator")
             idx = th.empty(batch_size, dtype=th.int64, device=self.device)
+            if self._sample_ws is not None:
+                L.check(L.lib().uavgnn_replay_sample_wide(self.state.data_ptr(), self.rng.data_ptr(), self.capacity, batch_size,
+                                                          idx.data_ptr(), self.status.data_ptr(), self._sample_ws.data_ptr(), L.stream()),
+                        "uavgnn_replay_sample_wide")
+                return idx
             L.check(L.lib().uavgnn_replay_sample(self.state.data_ptr(), self.rng.data_ptr(), self.capacity, batch_size,
                                                  idx.data_ptr(), self.status.data_ptr(), L.stream()), "uavgnn_replay_sample")
             return idx
@@ -159,6 +181,7 @@ class SequenceReplay(_RingState):
         T, n, M = max_seq_len, n_agents, n_gts
         self.capacity, self.T, self.n, self.M, self.n_envs = capacity, T, n, M, n_envs
         self.r_comm, self.device = r_comm, th.device(device)
+        self._check_device_state(device_state)
         f = dict(dtype=th.float32, device=self.device)
         rd = n if rew_dim is None else rew_dim
 
@@ -242,6 +265,7 @@ class SingleUbsSequenceReplay(_RingState):
         T, M = max_seq_len, n_gts
         self.capacity, self.T, self.M, self.n_envs = capacity, T, M, n_envs
         self.device = th.device(device)
+        self._check_device_state(device_state)
         f = dict(dtype=th.float32, device=self.device)
 
         def ring(lead):  # committed sequences / sequences under construction (one per parallel env)
