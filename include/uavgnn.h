@@ -328,6 +328,25 @@ int uavgnn_replay_sample_wide(const long long* state, long long* rng, int capaci
                               void* workspace, uavgnn_stream_t stream);
 int uavgnn_replay_gather(const long long* fields, int n_fields, const long long* idx, int B, uavgnn_stream_t stream);
 
+/* ---- compact replay ring: observations rebuilt from simulator state (csrc/replay_rebuild.hip) -----------------------
+ * The padded observations and the global state of B sampled sequences, written TIME-MAJOR as the update's buffers hold them, from
+ * the four arrays the multi-UBS simulator computes them from (reference: envs/mubs_cov/mubs_cov.py:212-297 get_obs / get_state; the
+ * batch of algos/madrqn/learner.py:99-116): ring fields pos_ubs [n_seq, steps, n, 2] f64, rate / avg [n_seq, steps, M] f32
+ * (rate_per_gt and avg_rate AFTER the step's update), pos_gts [n_seq, M, 2] f32 (constant within a sequence).  For step t < steps
+ * and row b < B, with s = idx[b] clamped into [0, n_seq) as uavgnn_replay_gather clamps:
+ *   obs_gt [steps, B, n, M, Sg], obs_ubs [steps, B, n, n-1, 3], obs_agent [steps, B, n, 2], d_u2u [steps, B, n, n] (may be NULL),
+ *   state [steps, B, uavgnn_env_state_dim] (may be NULL)
+ * hold the BITS uavgnn_env_step wrote for that state: the same operations in the same types (float64 norms rounded to float32,
+ * visibility by d <= float(r_sns) / float(r_comm), float64 divisions).  int_consts / f64_consts: the HOST arrays of uavgnn_env_step.
+ * Sg: the last extent of obs_gt, 5 with fair_service and 4 without - anything else, a null argument (obs_ubs may be NULL when
+ * n == 1), n_seq < 1, steps < 1 or B < 0: UAVGNN_EINVAL.  n <= 16, M <= 1024, else UAVGNN_EUNSUPPORTED.  One launch, no host
+ * synchronisation, nothing allocated: it captures into a hipGraph.  Stores are 16 bytes wide where a field's floats per (step, row)
+ * are a multiple of four and its base is 16-byte aligned, else 4 bytes.  B == 0: no launch. */
+int uavgnn_replay_rebuild_obs(const int32_t* int_consts, const double* f64_consts, const double* pos_ubs, const float* rate,
+                              const float* avg, const float* pos_gts, int n_seq, int steps, const long long* idx, int B,
+                              float* obs_gt, int Sg, float* obs_ubs, float* obs_agent, float* d_u2u, float* state,
+                              uavgnn_stream_t stream);
+
 /* ---- bias gradients ---------------------------------------------------------------------------------------------
  * acc[s, :] += column sums of the rows [s*R, (s+1)*R) of x[N, C] (row stride ld, unit column stride), R = ceil(N / S).
  * The db = dY.sum(0) of the Linear / GRUCell backward (gnn_agents.py:43-46,:237-246 under learner.py:157), accumulated
@@ -516,8 +535,8 @@ int uavgnn_adamw_polyak(float* p, float* g, float* exp_avg, float* exp_avg_sq, f
  * priorities used by this step -> priorities for the next one), avg_rate [B,M], t [B], run_f32 [B,4] = {total throughput,
  * average global utility, Jain index, global utility}, n_colls [B].  Outputs: d_u2g [B,n,M], d_u2u [B,n,n], gt_ubs /
  * gt_rb [B,M] (serving UBS / resource block per GT, -1 = unserved), rate_per_gt [B,M], rate_per_ubs [B,n] f64,
- * mask_collision [B,n], reward [B,n] f64, done [B], padded observations obs_gt [B,n,M,5|4], obs_ubs [B,n,n-1,3],
- * obs_agent [B,n,2] (column 0 = visibility flag: the input format of uavgnn_obs_degrees / _compact) and the global state
+ * mask_collision [B,n], reward [B,n] f64, done [B], padded observations obs_gt [B,n,M,5|4], obs_ubs [B,n,n-1,3] (holds
+ * nothing and may be NULL when n == 1), obs_agent [B,n,2] (column 0 = visibility flag: the input format of uavgnn_obs_degrees / _compact) and the global state
  * [B, uavgnn_env_state_dim] (may be NULL).  int_consts / f64_consts: HOST arrays, layout in csrc/env_sim.hip. */
 int uavgnn_env_state_dim(int n_ubs, int n_gts, int fair_service);
 int uavgnn_env_step(const int32_t* int_consts, const double* f64_consts, int B, const long long* actions,

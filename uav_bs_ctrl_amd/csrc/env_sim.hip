@@ -336,8 +336,9 @@ extern "C" int uavgnn_env_step(const int32_t* int_consts, const double* f64_cons
                                float* obs_agent, float* state, uavgnn_stream_t stream) {
   if (!int_consts || !f64_consts || B < 0 || !pos_ubs || !pos_gts || !prior || !avg_rate || !t || !run_f32 || !n_colls ||
       !d_u2g || !d_u2u || !gt_ubs || !gt_rb || !rate_per_gt || !rate_per_ubs || !mask_collision || !reward || !done ||
-      !obs_gt || !obs_ubs || !obs_agent || (actions && !avail_moves))
+      !obs_gt || !obs_agent || (actions && !avail_moves))
     return UAVGNN_EINVAL;
+  if (!obs_ubs && int_consts[0] != 1) return UAVGNN_EINVAL;   // one UBS: obs_ubs [B,1,0,3] holds nothing, its pointer may be null
   EnvConsts c;
   c.n = int_consts[0]; c.M = int_consts[1]; c.R = int_consts[2]; c.A = int_consts[3]; c.episode_limit = int_consts[4];
   c.fair_service = int_consts[5]; c.avoid_collision = int_consts[6];

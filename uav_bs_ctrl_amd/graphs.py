@@ -378,7 +378,7 @@ class GraphedUpdate(_GraphedUpdateBase):
         build = self._build
         obs = [build(o.gt[t], o.ubs[t], o.agent[t], None if o.d_u2u is None else o.d_u2u[t], self.r_comm, static=True)
                for t in range(T + 1)]
-        flat = lambda x, lo: x[lo:].reshape((-1,) + x.shape[2:])  # noqa: E731
+        flat = lambda x, lo: x[lo:].reshape(((x.shape[0] - lo) * x.shape[1],) + x.shape[2:])  # noqa: E731  (no -1: ubs is empty at n = 1)
         obs_all = build(flat(o.gt, 0), flat(o.ubs, 0), flat(o.agent, 0), None, self.r_comm, static=True)
         obs_next = build(flat(o.gt, 1), flat(o.ubs, 1), flat(o.agent, 1), None, self.r_comm, static=True)
         out = dict(obs=obs, obs_all=obs_all, obs_all_next=obs_next, h0=self.h0, h1=self.h1, acts=self.acts,
@@ -533,6 +533,8 @@ class Episode(_EnvObs):
     'gnn' / 'rnn' (exp1).  ``idx`` keeps the last sampled batch, ``eps`` / ``t`` the exploration rate and its counter.
     A learner with ``mixer=True`` (QMIX) trains here as well: the replay must store the simulator's ``state`` at the mixer's width and ONE
     shared reward (``state_dim=env.state_dim, rew_dim=1``, ``args.share_reward``), else ``ValueError``.
+    replay: a ``replay.CompactSequenceReplay`` (built ``for_env(env, ...)``) instead stages ``env.replay_state()`` and the hidden state at
+    every step and rebuilds observations and the mixer's state in its gather; it needs no stored ``state``, only ``rew_dim=1`` under QMIX.
 
     stats: a ``stats.EpochStats`` holding the info keys (EpRet, EpLen, AvgGlobalUtility, TotalThroughput, FairIdx, and ProbCollision for
     the multi-UBS simulator) and, when ``train``, LossQ: the body pushes the info tensors once at the end of the episode and LossQ after
@@ -566,12 +568,16 @@ class Episode(_EnvObs):
             raise ValueError("eps = (start, end, decay_steps): decay_steps must be positive")
         dev = learner.device
         self._bind_env(learner, env, enc)
+        self.compact = False
         if self.single:
             self.upd = GraphedSingleUbsUpdate(learner, self.batch_size, self.T, env.n_gts, enc, capture=False) if self.train else None
         else:
-            self.with_state = replay.mem["state"].shape[-1] > 0
+            from .replay import CompactSequenceReplay
+            # a compact ring stores the simulator's state, not its observations: nothing of `state` is staged, the gather rebuilds it
+            self.compact = isinstance(replay, CompactSequenceReplay)
+            self.with_state = not self.compact and replay.mem["state"].shape[-1] > 0
             if getattr(learner, "mixer", None) is not None:      # QMIX: q_tot is one value per environment, mixed from the stored global state
-                sd, rd = replay.mem["state"].shape[-1], replay.mem["rew"].shape[-1]
+                sd, rd = replay.state_dim if self.compact else replay.mem["state"].shape[-1], replay.mem["rew"].shape[-1]
                 if sd != learner.mixer.state_dim:
                     raise ValueError(f"replay: the mixer reads a state of width {learner.mixer.state_dim} but the replay stores "
                                      f"state_dim = {sd}")
@@ -599,6 +605,8 @@ class Episode(_EnvObs):
         o = env.observations()
         if self.single:
             rb.stage_obs(dict(gt=o["gt"], agent=o["agent"], h=h))
+        elif self.compact:
+            rb.stage_obs(dict(env.replay_state(), h=h.view(E, lr.n_agents, -1)))
         else:
             staged = dict(gt=o["gt"], ubs=o["ubs"], agent=o["agent"], d_u2u=o["d_u2u"], h=h.view(E, lr.n_agents, -1))
             if self.with_state:
@@ -611,6 +619,8 @@ class Episode(_EnvObs):
         o2, rew, done, info = env.step(acts)
         if self.single:
             lr.cache(rb, None, None, acts, rew, o2, h2, done, info["BadMask"], staged=True)
+        elif self.compact:
+            lr.cache(rb, None, None, None, acts, rew, env.replay_state(), h2, None, done, info["BadMask"], staged=True)
         else:
             st = o2["state"] if self.with_state else None      # `cache` stores next_state only when a state is given (staged: not read)
             lr.cache(rb, None, None, st, acts, rew, o2, h2, st, done, info["BadMask"], staged=True)

@@ -225,7 +225,7 @@ class MultiAgentQLearner:
                   next_h=(1.0 - done_raw).unsqueeze(2) * f32(next_h).reshape(E, n, -1))
         if not staged:
             tr["h"] = f32(h).reshape(E, n, -1)
-        for k in ("gt", "ubs", "agent", "d_u2u"):
+        for k in buffer.step_fields:         # the ring's own per-step observation fields: padded observations, or simulator state
             if not staged:
                 tr[k] = obs[k]
             tr["next_" + k] = next_obs[k]

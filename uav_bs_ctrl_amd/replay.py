@@ -14,6 +14,9 @@ Storage per sequence at 8 x 80, T = 50:  51*8*80*5*4 B = 653 KB of GT rows (+ 4 
 ``device_state=True`` (opt-in) moves what was left on the host - the ring position, the sampler, the batch's way into a captured update
 - to the device (csrc/replay.hip), so that a hipGraph can hold commits, samples and gathers (``graphs.GraphedEpisode``); the default keeps
 the host path as it was.
+
+``CompactSequenceReplay`` (opt-in, device-state only) stores the simulator state the observations are a pure function of - 48.7 KB per
+sequence at 8 x 50, T = 50, H = 256 against 881 KB - and rebuilds the update's buffers in its gather (csrc/replay_rebuild.hip), bit for bit.
 """
 from __future__ import annotations
 
@@ -174,6 +177,7 @@ class _RingState:
 
 class SequenceReplay(_RingState):
     _scheme, _obs_fields = SCHEME, ("gt", "ubs", "agent", "d_u2u", "h", "state")
+    step_fields = ("gt", "ubs", "agent", "d_u2u")    # what ``learner.cache`` takes from ``obs`` / ``next_obs``
 
     def __init__(self, capacity: int, max_seq_len: int, n_agents: int, n_gts: int, hidden_size: int,
                  n_envs: int = 1, state_dim: int = 0, r_comm: float = float("inf"), rew_dim: Optional[int] = None,
@@ -223,7 +227,7 @@ class SequenceReplay(_RingState):
                    dones=m["done"].permute(1, 0, 2).contiguous(), states=m["state"].permute(1, 0, 2).contiguous())
         if enc == "mlp":
             tm = {k: self.mem[k].transpose(0, 1).index_select(1, idx) for k in obs_keys}              # [T+1, B, ...]
-            rows = lambda x, lo: x[lo:].reshape((-1,) + x.shape[2:])  # noqa: E731
+            rows = lambda x, lo: x[lo:].reshape(((x.shape[0] - lo) * x.shape[1],) + x.shape[2:])  # noqa: E731  (no -1: ubs is empty at n = 1)
             out["obs"] = [from_padded_obs_flat(tm["gt"][t], tm["ubs"][t], tm["agent"][t], tm["d_u2u"][t], self.r_comm)
                           for t in range(T + 1)]
             out["obs_all"] = from_padded_obs_flat(rows(tm["gt"], 0), rows(tm["ubs"], 0), rows(tm["agent"], 0))
@@ -242,6 +246,139 @@ class SequenceReplay(_RingState):
                     gs.append(from_obs_dicts(o, m["d_u2u"][b, t].numpy(), self.r_comm))
                 obs.append(hb_batch(gs))
         out["obs"] = obs
+        return out
+
+    def sample(self, batch_size: int, generator: Optional[th.Generator] = None, enc: str = "gnn") -> Dict:
+        return self.gather(self.sample_indices(batch_size, generator), enc)
+
+
+COMPACT_SCHEME = ("pos_ubs", "rate", "avg", "pos_gts", "h", "act", "rew", "done")
+
+
+def compact_bytes_per_sequence(n: int, M: int, T: int, H: int, rd: int) -> int:
+    """Bytes of one sequence of a ``CompactSequenceReplay``: T+1 steps of pos_ubs [n,2] f64 and rate / avg [M] f32, pos_gts [M,2] f32
+    once, h [2,n,H] f32, act [T,n] int64, rew [T,rd] and done [T,1] f32."""
+    return (T + 1) * (16 * n + 8 * M) + 8 * M + 8 * n * H + 8 * T * n + 4 * T * rd + 4 * T
+
+
+class CompactSequenceReplay(_RingState):
+    """Opt-in ring of the multi-UBS experiments that stores what the simulator computes its observations FROM instead of the
+    observations: per step pos_ubs [n,2] f64, rate [M] and avg [M] (``BatchedUbsCoverageEnv.replay_state()``), per sequence pos_gts
+    [M,2] (staged at step 0) and the two hidden states an update reads, h [2,n,H] (steps 0 and 1), plus act / rew / done.  No ``state``
+    field, also under QMIX.  ``gather_into`` REBUILDS gt / ubs / agent / d_u2u / state of the sampled sequences straight into the
+    update's time-major buffers with one launch (uavgnn_replay_rebuild_obs: the arithmetic of the simulator step, so the same bits a
+    ``SequenceReplay`` would have copied) and moves h0 / h1 / act / rew / done with the existing gather launch.  48.7 KB per sequence
+    at 8 x 50, T = 50, H = 256 against 881 KB (``bytes_per_sequence``).
+
+    CONTRACT: a sequence never spans a reset - pos_gts is stored once per sequence, and it changes only at a reset.
+    ``graphs.Episode`` enforces ``episode_limit % T == 0`` and resets at the start of an episode, so its sequences never do.
+
+    Device-state only (``device_state=True`` on the GPU: commit, samplers and gather of ``_RingState``); built from the environment so
+    that the map's constants and shapes cannot disagree with the simulator's:
+
+        rb = CompactSequenceReplay.for_env(env, capacity, max_seq_len, hidden_size, rew_dim=None, seed=None)     # n_envs = env.B
+    """
+    _scheme, _obs_fields = COMPACT_SCHEME, ("pos_ubs", "rate", "avg")
+    step_fields = ("pos_ubs", "rate", "avg", "pos_gts")      # what ``learner.cache`` takes from ``obs`` / ``next_obs``
+
+    def __init__(self, env, capacity: int, max_seq_len: int, hidden_size: int, rew_dim: Optional[int] = None,
+                 device_state: bool = True, seed: Optional[int] = None):
+        if not device_state:
+            raise ValueError("CompactSequenceReplay: device_state=True only (the rebuild is a device launch; no host path exists)")
+        T, n, M = max_seq_len, env.n_agents, env.n_gts
+        self.capacity, self.T, self.n, self.M, self.n_envs = capacity, T, n, M, env.B
+        self.r_comm, self.device = env.p.r_comm, th.device(env.device)
+        if self.device.type != "cuda":
+            raise ValueError("CompactSequenceReplay: the ring, its counters and the rebuild live on the GPU (no CPU fallback exists)")
+        self._check_device_state(True)
+        self._ic, self._fc = env._ic, env._fc                # the constant arrays uavgnn_env_step takes
+        self.Sg, self.state_dim, self.hidden_size = env.out["obs_gt"].shape[-1], env.state_dim, hidden_size
+        self.rew_dim = n if rew_dim is None else rew_dim
+        f = dict(dtype=th.float32, device=self.device)
+
+        def ring(lead):  # committed sequences / sequences under construction (one per parallel env)
+            return dict(pos_ubs=th.zeros(lead, T + 1, n, 2, dtype=th.float64, device=self.device), rate=th.zeros(lead, T + 1, M, **f),
+                        avg=th.zeros(lead, T + 1, M, **f), pos_gts=th.zeros(lead, M, 2, **f), h=th.zeros(lead, 2, n, hidden_size, **f),
+                        act=th.zeros(lead, T, n, dtype=th.int64, device=self.device), rew=th.zeros(lead, T, self.rew_dim, **f),
+                        done=th.zeros(lead, T, 1, **f))
+        self.mem = ring(capacity)
+        self.cur = ring(self.n_envs)
+        self._init_ring_state(True, seed)
+
+    @classmethod
+    def for_env(cls, env, capacity: int, max_seq_len: int, hidden_size: int, rew_dim: Optional[int] = None, seed: Optional[int] = None):
+        return cls(env, capacity, max_seq_len, hidden_size, rew_dim, True, seed)
+
+    @property
+    def bytes_per_sequence(self) -> int:
+        return compact_bytes_per_sequence(self.n, self.M, self.T, self.hidden_size, self.rew_dim)
+
+    def stage_obs(self, tr: Dict[str, th.Tensor]) -> None:
+        """The step fields at the current step; pos_gts at step 0 only (constant until the next reset); h at steps 0 and 1 only."""
+        super().stage_obs(tr)
+        if self.ptr == 0 and "pos_gts" in tr:
+            self.cur["pos_gts"].copy_(tr["pos_gts"])
+        if self.ptr < 2 and "h" in tr:
+            self.cur["h"][:, self.ptr] = tr["h"]
+
+    def push(self, tr: Dict[str, th.Tensor]) -> None:
+        if self.T == 1 and "next_h" in tr:       # the only sequence length whose h[1] is the hidden state AFTER the last transition
+            self.cur["h"][:, 1] = tr["next_h"]
+        super().push(tr)
+
+    def _gather_fields(self, target, B: int):
+        m, T = self.mem, self.T
+        return [("h0", m["h"], 0, target.h0, 1), ("h1", m["h"], 1, target.h1, 1), ("act", m["act"], 0, target.acts, T),
+                ("rew", m["rew"], 0, target.rews, T), ("done", m["done"], 0, target.dones, T)]
+
+    def rebuild_into(self, idx: th.Tensor, gt: th.Tensor, ubs: th.Tensor, agent: th.Tensor, d_u2u: Optional[th.Tensor] = None,
+                     state: Optional[th.Tensor] = None) -> None:
+        """The observations of the sequences ``idx`` into time-major buffers gt [T+1,B,n,M,Sg], ubs [T+1,B,n,n-1,3], agent [T+1,B,n,2]
+        and, where given, d_u2u [T+1,B,n,n] and state [T+1,B,state_dim]: ONE launch (uavgnn_replay_rebuild_obs), capturable."""
+        if idx.dtype != th.int64 or not idx.is_contiguous():
+            raise ValueError("idx: a contiguous int64 tensor expected")
+        L.require_gpu(idx)
+        B, T1, n, M = idx.numel(), self.T + 1, self.n, self.M
+        shapes = dict(gt=(gt, (n, M, self.Sg)), ubs=(ubs, (n, max(n - 1, 0), 3)), agent=(agent, (n, 2)), d_u2u=(d_u2u, (n, n)),
+                      state=(state, (self.state_dim,)))
+        for name, (x, tail) in shapes.items():
+            if x is not None and (tuple(x.shape) != (T1, B) + tail or x.dtype != th.float32 or not x.is_contiguous() or not x.is_cuda):
+                raise ValueError(f"rebuild_into: {name}: a contiguous float32 buffer {(T1, B) + tail} on the GPU expected, got "
+                                 f"{tuple(x.shape)} {x.dtype}")
+        m = self.mem
+        L.check(L.lib().uavgnn_replay_rebuild_obs(self._ic, self._fc, m["pos_ubs"].data_ptr(), m["rate"].data_ptr(), m["avg"].data_ptr(),
+                                                  m["pos_gts"].data_ptr(), self.capacity, T1, idx.data_ptr(), B, gt.data_ptr(), self.Sg,
+                                                  L.ptr(ubs) or None, agent.data_ptr(), L.ptr(d_u2u), L.ptr(state), L.stream()),
+                "uavgnn_replay_rebuild_obs")
+
+    def gather_into(self, idx: th.Tensor, target) -> None:
+        """The update's buffers of ``target`` (a ``graphs.GraphedUpdate``) from the sequences ``idx``: the rebuild launch for ``obs.*`` and
+        ``states``, the gather launch for h0 / h1 / acts / rews / dones.  Same bits as ``SequenceReplay.gather_into`` on a ring that
+        stored the simulator's observations."""
+        o = target.obs
+        self.rebuild_into(idx, o.gt, o.ubs, o.agent, o.d_u2u, getattr(target, "states", None))
+        super().gather_into(idx, target)
+
+    def gather(self, idx: th.Tensor, enc: str = "gnn") -> Dict:
+        """The batch dict ``SequenceReplay.gather`` returns, over rebuilt time-major tensors (``states``: always, [T+1, B, state_dim])."""
+        B, T, n, M = idx.numel(), self.T, self.n, self.M
+        if enc not in ("gnn", "mlp"):
+            raise ValueError(f"enc must be 'gnn' or 'mlp', got {enc!r}")
+        f = dict(dtype=th.float32, device=self.device)
+        gt, ubs = th.empty(T + 1, B, n, M, self.Sg, **f), th.empty(T + 1, B, n, max(n - 1, 0), 3, **f)
+        agent, d_u2u, states = th.empty(T + 1, B, n, 2, **f), th.empty(T + 1, B, n, n, **f), th.empty(T + 1, B, self.state_dim, **f)
+        self.rebuild_into(idx, gt, ubs, agent, d_u2u, states)
+        m = {k: self.mem[k].index_select(0, idx) for k in ("h", "act", "rew", "done")}
+        out = dict(h0=m["h"][:, 0].reshape(B * n, -1), h1=m["h"][:, 1].reshape(B * n, -1),
+                   acts=m["act"].permute(1, 0, 2).reshape(T, B * n, 1), rews=m["rew"].permute(1, 0, 2).contiguous(),
+                   dones=m["done"].permute(1, 0, 2).contiguous(), states=states)
+        if enc == "mlp":
+            rows = lambda x, lo: x[lo:].reshape(((x.shape[0] - lo) * x.shape[1],) + x.shape[2:])  # noqa: E731  (no -1: ubs is empty at n = 1)
+            out["obs"] = [from_padded_obs_flat(gt[t], ubs[t], agent[t], d_u2u[t], self.r_comm) for t in range(T + 1)]
+            out["obs_all"] = from_padded_obs_flat(rows(gt, 0), rows(ubs, 0), rows(agent, 0))
+            out["obs_all_next"] = from_padded_obs_flat(rows(gt, 1), rows(ubs, 1), rows(agent, 1))
+            return out
+        out["obs"] = [from_padded_obs(gt[t], ubs[t], agent[t], d_u2u[t], self.r_comm) for t in range(T + 1)]
         return out
 
     def sample(self, batch_size: int, generator: Optional[th.Generator] = None, enc: str = "gnn") -> Dict:

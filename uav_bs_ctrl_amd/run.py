@@ -4,7 +4,7 @@ log rows, checkpoints, trajectory films and resume.
     run = Run.create(exp="exp3", env="8ubs", args=args, output_dir="data/exp3_8ubs_s0", seed=0, n_envs=32)
     run.train()                          # all remaining epochs; run.train(epochs=k): k more
     run = Run.resume("data/exp3_8ubs_s0")    # rebuilds everything from config.json + state.pt and goes on, bit for bit
-    python -m uav_bs_ctrl_amd.run --exp exp3 --env 8ubs --args-json args.json --out data/exp3_8ubs_s0 [--seed 0 --envs 32 --resume --eager]
+    python -m uav_bs_ctrl_amd.run --exp exp3 --env 8ubs --args-json args.json --out data/exp3_8ubs_s0 [--seed 0 --envs 32 --resume --eager --compact-replay]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N -m uav_bs_ctrl_amd.run ...     # data-parallel: N ranks, one GPU each
 
 This is host orchestration over launches that exist: a collect-only and a training ``graphs.GraphedEpisode``, one
@@ -303,6 +303,20 @@ def _reference_env(exp: str, env) -> tuple:
                                        avoid_collision=bool(p.avoid_collision))
 
 
+def run_config(exp: str, env, ns, seed: int = 0, n_envs: int = 32, n_test_envs: Optional[int] = None, updates_per_segment: int = 1,
+               graphed: bool = True, save_replay: bool = True, world: int = 1, force_collective: bool = False,
+               compact_replay: bool = False) -> dict:
+    """The ``uav_bs_ctrl_amd`` entry of ``config.json``: everything of ``Run.create``'s arguments that ``Run.resume`` needs to rebuild the
+    same run (host only).  compact_replay with exp1 is a ``ValueError``: the single-UBS observations are M x 4 floats already."""
+    if compact_replay and exp == "exp1":
+        raise ValueError("compact_replay: the compact ring stores the multi-UBS simulator's state (exp2 / exp3); exp1's observations "
+                         "are already n_gts x 4 floats per step")
+    return dict(exp=exp, env=_env_to_config(exp, env), n_envs=int(n_envs),
+                n_test_envs=int(ns.num_test_episodes if n_test_envs is None else n_test_envs),
+                updates_per_segment=int(updates_per_segment), graphed=bool(graphed), save_replay=bool(save_replay),
+                seeds=derive_seeds(seed), world=int(world), force_collective=bool(force_collective), compact_replay=bool(compact_replay))
+
+
 # ---- the driver -------------------------------------------------------------------------------------------------------------------------
 class Run:
     """One training run and its directory.  Build it with ``Run.create`` or ``Run.resume``.
@@ -323,7 +337,7 @@ class Run:
         from .film import Film
         from .graphs import Episode, Evaluation, GraphedEpisode, GraphedEvaluation, info_keys
         from .learner import MultiAgentQLearner, QLearner
-        from .replay import SequenceReplay, SingleUbsSequenceReplay
+        from .replay import CompactSequenceReplay, SequenceReplay, SingleUbsSequenceReplay
         from .sim import BatchedSingleUbsCoverageEnv, BatchedUbsCoverageEnv
         from .stats import EpochStats
         self.ours, self.args, self.output_dir, self.exp_name = ours, args, output_dir, exp_name
@@ -342,6 +356,9 @@ class Run:
         exp, E, seeds = ours["exp"], int(ours["n_envs"]), _rank_seeds(ours["seeds"], self.rank)      # config.json holds rank 0's
         self.exp, self.single, self.seeds, self.save_replay = exp, exp == "exp1", seeds, bool(ours["save_replay"])
         E_test = int(ours["n_test_envs"])
+        self.compact_replay = bool(ours.get("compact_replay", False))     # absent in a config.json written before the option existed
+        if self.compact_replay and self.single:
+            raise ValueError("compact_replay: the compact ring stores the multi-UBS simulator's state (exp2 / exp3), not exp1's")
         if getattr(args, "mixer", False):
             raise ValueError("mixer = True is not covered by the driver yet: graphs.Episode / GraphedEpisode train with a mixer, "
                              "Run does not build one")
@@ -370,6 +387,9 @@ class Run:
         if self.single:
             self.replay = SingleUbsSequenceReplay(int(args.replay_size), T, env.n_gts, args.hidden_size, n_envs=E, device=dev,
                                                   device_state=True, seed=seeds["replay"])
+        elif self.compact_replay:                # simulator state instead of observations: the same update inputs, bit for bit
+            self.replay = CompactSequenceReplay.for_env(env, int(args.replay_size), T, args.hidden_size,
+                                                        rew_dim=1 if args.share_reward else None, seed=seeds["replay"])
         else:
             self.replay = SequenceReplay(int(args.replay_size), T, env.n_agents, env.n_gts, args.hidden_size, n_envs=E,
                                          r_comm=env.p.r_comm, rew_dim=1 if args.share_reward else None, device=dev,
@@ -398,13 +418,15 @@ class Run:
     @classmethod
     def create(cls, exp: str, env, args, output_dir: str, exp_name: Optional[str] = None, seed: int = 0, n_envs: int = 32,
                n_test_envs: Optional[int] = None, updates_per_segment: int = 1, graphed: bool = True, save_replay: bool = True,
-               group=None, force_collective: bool = False) -> "Run":
+               group=None, force_collective: bool = False, compact_replay: bool = False) -> "Run":
         """Builds simulators, learner, replay, statistics, film and the three graphs (``graphed=False``: their eager forms) as
         run.py:47-61 builds them and writes ``config.json``; sets torch's generator (``torch.manual_seed(seed)``, as the reference's
         ``set_rand_seed`` does) for the parameter initialisation.  env: a map id of ``sim.MAPS`` or a ``MapSpec`` (exp2 / exp3), a
         ``SingleUbsParams`` (exp1).  n_test_envs: evaluation environments (default ``num_test_episodes``; must divide it).
         save_replay=False: ``state.pt`` leaves the ring out (gigabytes at exp3 sizes); a resumed run then collects ``update_after_eff``
         interactions again before it trains and is NOT bit-identical to an uninterrupted one.
+        compact_replay=True (exp2 / exp3): the ring is a ``replay.CompactSequenceReplay`` - simulator state instead of observations,
+        about 18 x fewer bytes per sequence in HBM and in ``state.pt``, the same update inputs bit for bit; exp1: ``ValueError``.
 
         With ``torch.distributed`` initialised the run is data-parallel over ``group`` (default: the world) and EVERY rank calls
         ``create`` with the same arguments but its own ``args.device``; ``n_envs`` and ``args.batch_size`` are per rank.
@@ -412,10 +434,8 @@ class Run:
         import torch.distributed as dist
         ns = check_args(exp, args)
         world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
-        ours = dict(exp=exp, env=_env_to_config(exp, env), n_envs=int(n_envs),
-                    n_test_envs=int(ns.num_test_episodes if n_test_envs is None else n_test_envs),
-                    updates_per_segment=int(updates_per_segment), graphed=bool(graphed), save_replay=bool(save_replay),
-                    seeds=derive_seeds(seed), world=int(world), force_collective=bool(force_collective))
+        ours = run_config(exp, env, ns, seed, n_envs, n_test_envs, updates_per_segment, graphed, save_replay, world, force_collective,
+                          compact_replay)
         run = cls(ours, ns, output_dir, exp_name, resuming=False, group=group)
         if run.rank == 0:
             env_fn, env_kwargs = _reference_env(exp, env)
@@ -628,7 +648,7 @@ def _parse_env(exp: str, text: str):
     return SingleUbsParams(n_grps=g, gts_per_grp=s)
 
 
-def main(argv=None) -> None:
+def _parser():
     import argparse
     ap = argparse.ArgumentParser(prog="python -m uav_bs_ctrl_amd.run", description=__doc__.split("\n\n")[0])
     ap.add_argument("--out", required=True, help="the run directory")
@@ -643,10 +663,17 @@ def main(argv=None) -> None:
     ap.add_argument("--exp-name", default=None)
     ap.add_argument("--eager", action="store_true", help="graphs.Episode / Evaluation instead of their graphs")
     ap.add_argument("--no-save-replay", action="store_true")
+    ap.add_argument("--compact-replay", action="store_true",
+                    help="exp2 / exp3: the ring stores simulator state and rebuilds the observations (replay.CompactSequenceReplay)")
     ap.add_argument("--epochs", type=int, default=None, help="run this many more epochs, not all remaining ones")
     ap.add_argument("--dist-backend", choices=("nccl", "gloo"), default="nccl", help="under a launcher that sets RANK: the backend of the group")
     ap.add_argument("--dist-timeout", type=float, default=600.0, help="seconds after which a collective gives up on a missing rank")
     ap.add_argument("--one-device", action="store_true", help="every rank stays on args.device instead of cuda:{LOCAL_RANK}")
+    return ap
+
+
+def main(argv=None) -> None:
+    ap = _parser()
     a = ap.parse_args(argv)
     if not a.resume and not (a.exp and a.env and a.args_json):
         ap.error("--exp, --env and --args-json are required without --resume")
@@ -661,7 +688,7 @@ def main(argv=None) -> None:
                 args["device"] = device
             run = Run.create(a.exp, _parse_env(a.exp, a.env), args, a.out, exp_name=a.exp_name or a.exp, seed=a.seed, n_envs=a.envs,
                              n_test_envs=a.test_envs, updates_per_segment=a.updates_per_segment, graphed=not a.eager,
-                             save_replay=not a.no_save_replay)
+                             save_replay=not a.no_save_replay, compact_replay=a.compact_replay)
         run.train(a.epochs)
         if run.rank == 0:
             print(f"{a.out}: epoch {run.epoch} of {run.plan.epochs}, {run.interacts} interactions, {run.elapsed:.1f} s")

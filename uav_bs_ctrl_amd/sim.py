@@ -255,6 +255,13 @@ class BatchedUbsCoverageEnv:
         o = self.out
         return dict(gt=o["obs_gt"], ubs=o["obs_ubs"], agent=o["obs_agent"], d_u2u=o["d_u2u"], state=o["state"])
 
+    def replay_state(self) -> Dict[str, th.Tensor]:
+        """What ``observations()`` is a pure function of, beside the map's constants: pos_ubs [B,n,2] f64, rate [B,M] (this step's
+        ``rate_per_gt``), avg [B,M] (``avg_rate`` after this step's update), pos_gts [B,M,2] (constant within an episode) - the step
+        fields of ``replay.CompactSequenceReplay``.  VIEWS of the simulator's own buffers: no copy, no launch; the next step overwrites
+        them in place."""
+        return dict(pos_ubs=self.pos_ubs, rate=self.out["rate_per_gt"], avg=self.avg_rate, pos_gts=self.pos_gts)
+
     def graph(self, with_comm: bool = True, static: bool = False):
         """HeteroBatch of the current observations, built on the device (f1)."""
         o = self.out
