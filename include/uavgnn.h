@@ -537,7 +537,11 @@ int uavgnn_adamw_polyak(float* p, float* g, float* exp_avg, float* exp_avg_sq, f
  * gt_rb [B,M] (serving UBS / resource block per GT, -1 = unserved), rate_per_gt [B,M], rate_per_ubs [B,n] f64,
  * mask_collision [B,n], reward [B,n] f64, done [B], padded observations obs_gt [B,n,M,5|4], obs_ubs [B,n,n-1,3] (holds
  * nothing and may be NULL when n == 1), obs_agent [B,n,2] (column 0 = visibility flag: the input format of uavgnn_obs_degrees / _compact) and the global state
- * [B, uavgnn_env_state_dim] (may be NULL).  int_consts / f64_consts: HOST arrays, layout in csrc/env_sim.hip. */
+ * [B, uavgnn_env_state_dim] (may be NULL).  int_consts / f64_consts: HOST arrays,
+ *   int_consts [7]:  {n_ubs, n_gts, n_rbs, n_actions, episode_limit, fair_service, avoid_collision}
+ *   f64_consts [18]: {range_pos, r_cov, r_sns, r_comm, dt, h_ubs, p_tx, n0, bw, fc, a, b, eta_los, eta_nlos, safe_dist, penalty,
+ *                     reward_scale_rate, max_rate}
+ * (the indices have names in csrc/env_math.h, which decodes them for this entry and for uavgnn_replay_rebuild_obs). */
 int uavgnn_env_state_dim(int n_ubs, int n_gts, int fair_service);
 int uavgnn_env_step(const int32_t* int_consts, const double* f64_consts, int B, const long long* actions,
                     const double* avail_moves, double* pos_ubs, const float* pos_gts, int32_t* prior, float* avg_rate,

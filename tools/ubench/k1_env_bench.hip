@@ -1,14 +1,10 @@
 // Stand-alone timing of the fused K1 forward (csrc/gatv2_hetero.hip) at C3 size on SURVEY's degree distributions, without
 // Python: back-to-back launches between two events, whole kernel and phase ablations, + a checksum of the output so that
 // variants can be compared for equality.  argv[1]: dist (env | dense | zero), argv[2]: B (default 4096).
-// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Iuav_bs_ctrl_amd/csrc [-DK1_OLD] [-D...] tools/ubench/k1_env_bench.hip -o tools/ubench/bin/k1_env_bench[_pair]
+// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Iuav_bs_ctrl_amd/csrc [-D...] tools/ubench/k1_env_bench.hip -o tools/ubench/bin/k1_env_bench
 #define K1_ABLATE 1
 #define K1_STANDALONE 1
-#if defined(K1_OLD)   // the rounds 1-3 kernel (pairs of destinations per row tile in phase N): -DK1_OLD [-DK1_BF16Z=0]
-#include "../../uav_bs_ctrl_amd/csrc/gatv2_hetero_pair.inc"
-#else
 #include "../../uav_bs_ctrl_amd/csrc/gatv2_hetero.hip"
-#endif
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -53,10 +49,8 @@ static void* g_image = nullptr;
 static int k1_call(const float* xg, int Es, const int32_t* so, const int32_t* ord, const float* xu, int En, const int32_t* no,
                    const float* xa, int N, const float* const* ps, const float* const* pn, float* out, int ld, float* sv_s,
                    float* sv_n, int ph) {
-#if !defined(K1_OLD)
   if (g_image != nullptr)
     return uavgnn_gatv2_hetero_fwd_image(xg, Es, so, ord, xu, En, no, xa, N, ps, pn, 4, 64, 0.2f, g_image, out, ld, sv_s, sv_n, ph, nullptr);
-#endif
   return uavgnn_gatv2_hetero_fwd_phases(xg, Es, so, ord, xu, En, no, xa, N, ps, pn, 4, 64, 0.2f, out, ld, sv_s, sv_n, ph, nullptr);
 }
 
@@ -132,14 +126,12 @@ int main(int argc, char** argv) {
     printf("streaming write of %.1f MB, %4d blocks: plain %6.2f us (%.2f TB/s)  nontemporal %6.2f us (%.2f TB/s)\n", n4 * 16 / 1e6, g,
            t0, n4 * 16 / t0 / 1e6, t1, n4 * 16 / t1 / 1e6);
   }
-#if !defined(K1_OLD)
   if (getenv("K1_IMAGE")) {
     hipMalloc(&g_image, uavgnn_gatv2_hetero_image_bytes());
     const int rc = uavgnn_gatv2_hetero_prepare(ps, pn, 4, 64, 0.2f, g_image, nullptr);
     hipDeviceSynchronize();
     printf("prepared image: %zu bytes, rc %d\n", uavgnn_gatv2_hetero_image_bytes(), rc);
   }
-#endif
   for (int ph : {3, 3 | 4096, 3 | 8192, 3 | 12288, 2, 1, 0, 2 | 32, 2 | 64, 2 | 128, 2 | 32 | 64 | 128}) {
     auto run = [&] {
       int rc = k1_call(d_xg, Es, d_so, d_ord, d_xu, En, d_no, d_xa, N, ps, pn, out, 2 * H, nullptr, nullptr, ph);
@@ -168,7 +160,6 @@ int main(int argc, char** argv) {
     printf("phases %3d: %8.2f us  %7.1f GB/s alg (%.3f of 8 TB/s)   checksum %.9e  abs %.9e\n", ph, us, bytes / us / 1e3,
            bytes / us / 1e3 / 8000.0, cs, ca);
   }
-#if !defined(K1_OLD)
   {  // time line of the wavefronts of ONE launch (phases bit 10): 100 MHz stamps at entry, after the workgroup prologue, after the
      // phase-N operand loads, after the residual-only rows / the score tiles / the `near` rows of the first block were issued,
      // after the wave's stores have drained, after phase S
@@ -194,6 +185,5 @@ int main(int argc, char** argv) {
       }
     }
   }
-#endif
   return 0;
 }

@@ -17,15 +17,10 @@
 // priorities) the order of equal keys likewise depends on the SIMD dispatch.  This kernel uses the stable order in both places
 // (ties -> lower UBS / GT index first); tests/test_env_sim.py says how the fixtures pin it and keeps exact distance ties out of them.
 #include "common.h"
+#include "env_math.h"
 
 namespace uavgnn {
 namespace {
-
-struct EnvConsts {
-  int n, M, R, A, episode_limit, fair_service, avoid_collision, state_dim;
-  double range_pos, r_cov, r_sns, r_comm, dt, h_ubs, p_tx, n0, bw, fc, a, b, eta_los, eta_nlos, safe_dist, penalty,
-      rew_scale, max_rate;
-};
 
 // NumPy's pairwise float32 summation (numpy/_core/src/umath/loops_utils.h: pairwise_sum) over a contiguous run.
 __device__ float np_sum_f32(const float* a, int n) {
@@ -109,29 +104,22 @@ __global__ __launch_bounds__(kWave) void env_step_kernel(
   if (lane < n) CNT[lane] = 0;
   __syncthreads();
   const float* __restrict__ pg = pos_gts + static_cast<size_t>(b) * M * 2;
-  const double k_los = pow(10.0, c.eta_los / 20.0), k_nlos = pow(10.0, c.eta_nlos / 20.0);   // loop-invariant excess-loss factors
+  const double k_los = a2g_excess_loss(c.eta_los), k_nlos = a2g_excess_loss(c.eta_nlos);
   // ---- step 1: distances (:135-141), float64 norm of (float32 GT position - float64 UBS position), stored float32 ----
   for (int k = lane; k < n * M; k += kWave) {
     const int i = k / M, m = k - i * M;
     const double dx = static_cast<double>(pg[2 * m]) - PU[2 * i], dy = static_cast<double>(pg[2 * m + 1]) - PU[2 * i + 1];
-    const float d = static_cast<float>(sqrt(dx * dx + dy * dy));
+    const float d = dist_f32(dx, dy);
     DUG[k] = d;
     d_u2g_out[static_cast<size_t>(b) * n * M + k] = d;
-    // A2G channel gain (envs/common.py:49-59): arctan / exp in float32, path loss in float64 (np.square(h) is a float64)
-    const float ang = atanf(static_cast<float>(c.h_ubs) / (d + 1e-5f));
-    const float p_los = 1.f / (1.f + static_cast<float>(c.a) * expf(-static_cast<float>(c.b) * (ang - static_cast<float>(c.a))));
-    const double dd = sqrt(static_cast<double>(d * d) + c.h_ubs * c.h_ubs);
-    const double q = 4.0 * 3.141592653589793 * c.fc * dd / 3e8;
-    const double fspl = q * q;
-    const double pl = static_cast<double>(p_los) * fspl * k_los + static_cast<double>(1.f - p_los) * fspl * k_nlos;
-    const double ptxg = c.p_tx * (1.0 / pl);
+    const double ptxg = a2g_rx_power(c, d, k_los, k_nlos);   // A2G channel gain (envs/common.py:49-59)
     G[k] = ptxg;
     W[k] = d <= static_cast<float>(c.r_cov) ? static_cast<float>(ptxg) : 0.f;     // p_itf rows are float32 (:169,:187)
   }
   for (int k = lane; k < n * n; k += kWave) {
     const int i = k / n, jx = k - i * n;
     const double dx = PU[2 * jx] - PU[2 * i], dy = PU[2 * jx + 1] - PU[2 * i + 1];
-    const float d = static_cast<float>(sqrt(dx * dx + dy * dy));
+    const float d = dist_f32(dx, dy);
     DUU[k] = d;
     d_u2u_out[static_cast<size_t>(b) * n * n + k] = d;
   }
@@ -243,15 +231,7 @@ __global__ __launch_bounds__(kWave) void env_step_kernel(
   }
   __syncthreads();
   // next priorities (:209): STABLE ascending order of the averages
-  for (int m = lane; m < M; m += kWave) {
-    const float am = AVG[m];
-    int rank = 0;
-    for (int m2 = 0; m2 < M; ++m2) {
-      const float a2 = AVG[m2];
-      rank += (a2 < am) || (a2 == am && m2 < m);
-    }
-    prior[static_cast<size_t>(b) * M + rank] = m;
-  }
+  for (int m = lane; m < M; m += kWave) prior[static_cast<size_t>(b) * M + stable_rank(AVG, M, m)] = m;
   // ---- reward (:324-341), float64 from the float32 utility -----------------------------------------------------------
   if (lane < n) {
     float base;
@@ -273,11 +253,10 @@ __global__ __launch_bounds__(kWave) void env_step_kernel(
     float* o = obs_gt + (static_cast<size_t>(b) * n * M + k) * Sg;
     const bool vis = DUG[k] <= static_cast<float>(c.r_sns);
     o[0] = vis ? 1.f : 0.f;
-    o[1] = vis ? static_cast<float>((static_cast<double>(pg[2 * m]) - PU[2 * i]) / norm_s) : 0.f;
-    o[2] = vis ? static_cast<float>((static_cast<double>(pg[2 * m + 1]) - PU[2 * i + 1]) / norm_s) : 0.f;
-    o[3] = vis ? static_cast<float>(static_cast<double>(RATE[m]) / c.max_rate) : 0.f;
-    if (c.fair_service)
-      o[4] = vis ? static_cast<float>(static_cast<double>(AVG[m]) / c.max_rate * M / (n * R)) : 0.f;
+    o[1] = vis ? obs_offset(static_cast<double>(pg[2 * m]) - PU[2 * i], norm_s) : 0.f;
+    o[2] = vis ? obs_offset(static_cast<double>(pg[2 * m + 1]) - PU[2 * i + 1], norm_s) : 0.f;
+    o[3] = vis ? obs_rate(RATE[m], c.max_rate) : 0.f;
+    if (c.fair_service) o[4] = vis ? obs_avg_rate(AVG[m], c.max_rate, M, n, R) : 0.f;
   }
   for (int k = lane; k < n * (n - 1); k += kWave) {
     const int i = k / (n - 1), jj = k - i * (n - 1);
@@ -285,26 +264,26 @@ __global__ __launch_bounds__(kWave) void env_step_kernel(
     float* o = obs_ubs + (static_cast<size_t>(b) * n * (n - 1) + k) * 3;
     const bool vis = DUU[i * n + other] <= static_cast<float>(c.r_comm);
     o[0] = vis ? 1.f : 0.f;
-    o[1] = vis ? static_cast<float>((PU[2 * other] - PU[2 * i]) / norm_c) : 0.f;
-    o[2] = vis ? static_cast<float>((PU[2 * other + 1] - PU[2 * i + 1]) / norm_c) : 0.f;
+    o[1] = vis ? obs_offset(PU[2 * other] - PU[2 * i], norm_c) : 0.f;
+    o[2] = vis ? obs_offset(PU[2 * other + 1] - PU[2 * i + 1], norm_c) : 0.f;
   }
   if (lane < n) {
-    obs_agent[(static_cast<size_t>(b) * n + lane) * 2 + 0] = static_cast<float>(PU[2 * lane] / c.range_pos);
-    obs_agent[(static_cast<size_t>(b) * n + lane) * 2 + 1] = static_cast<float>(PU[2 * lane + 1] / c.range_pos);
+    obs_agent[(static_cast<size_t>(b) * n + lane) * 2 + 0] = obs_pos(PU[2 * lane], c.range_pos);
+    obs_agent[(static_cast<size_t>(b) * n + lane) * 2 + 1] = obs_pos(PU[2 * lane + 1], c.range_pos);
   }
   if (state_out != nullptr) {
     float* st = state_out + static_cast<size_t>(b) * c.state_dim;
     const int Ss = c.fair_service ? 4 : 3;
     if (lane < n) {
-      st[2 * lane] = static_cast<float>(PU[2 * lane] / c.range_pos);
-      st[2 * lane + 1] = static_cast<float>(PU[2 * lane + 1] / c.range_pos);
+      st[2 * lane] = obs_pos(PU[2 * lane], c.range_pos);
+      st[2 * lane + 1] = obs_pos(PU[2 * lane + 1], c.range_pos);
     }
     for (int m = lane; m < M; m += kWave) {
       float* g = st + 2 * n + m * Ss;
-      g[0] = pg[2 * m] / static_cast<float>(c.range_pos);
-      g[1] = pg[2 * m + 1] / static_cast<float>(c.range_pos);
-      g[2] = static_cast<float>(static_cast<double>(RATE[m]) / c.max_rate);
-      if (c.fair_service) g[3] = static_cast<float>(static_cast<double>(AVG[m]) / c.max_rate * M / (n * R));
+      g[0] = state_gt_pos(pg[2 * m], c.range_pos);
+      g[1] = state_gt_pos(pg[2 * m + 1], c.range_pos);
+      g[2] = obs_rate(RATE[m], c.max_rate);
+      if (c.fair_service) g[3] = obs_avg_rate(AVG[m], c.max_rate, M, n, R);
     }
   }
 }
@@ -325,9 +304,7 @@ extern "C" int uavgnn_env_state_dim(int n_ubs, int n_gts, int fair_service) {
   return 2 * n_ubs + n_gts * (fair_service ? 4 : 3);
 }
 
-// int_consts: {n_ubs, n_gts, n_rbs, n_actions, episode_limit, fair_service, avoid_collision}
-// f64_consts: {range_pos, r_cov, r_sns, r_comm, dt, h_ubs, p_tx, n0, bw, fc, a, b, eta_los, eta_nlos, safe_dist, penalty,
-//              reward_scale_rate, max_rate}
+// int_consts / f64_consts: layout in include/uavgnn.h, decoded by env_consts (csrc/env_math.h)
 extern "C" int uavgnn_env_step(const int32_t* int_consts, const double* f64_consts, int B, const long long* actions,
                                const double* avail_moves, double* pos_ubs, const float* pos_gts, int32_t* prior,
                                float* avg_rate, int32_t* t, float* run_f32, double* n_colls, float* d_u2g, float* d_u2u,
@@ -338,16 +315,8 @@ extern "C" int uavgnn_env_step(const int32_t* int_consts, const double* f64_cons
       !d_u2g || !d_u2u || !gt_ubs || !gt_rb || !rate_per_gt || !rate_per_ubs || !mask_collision || !reward || !done ||
       !obs_gt || !obs_agent || (actions && !avail_moves))
     return UAVGNN_EINVAL;
-  if (!obs_ubs && int_consts[0] != 1) return UAVGNN_EINVAL;   // one UBS: obs_ubs [B,1,0,3] holds nothing, its pointer may be null
-  EnvConsts c;
-  c.n = int_consts[0]; c.M = int_consts[1]; c.R = int_consts[2]; c.A = int_consts[3]; c.episode_limit = int_consts[4];
-  c.fair_service = int_consts[5]; c.avoid_collision = int_consts[6];
-  c.state_dim = uavgnn_env_state_dim(c.n, c.M, c.fair_service);
-  c.range_pos = f64_consts[0]; c.r_cov = f64_consts[1]; c.r_sns = f64_consts[2]; c.r_comm = f64_consts[3];
-  c.dt = f64_consts[4]; c.h_ubs = f64_consts[5]; c.p_tx = f64_consts[6]; c.n0 = f64_consts[7]; c.bw = f64_consts[8];
-  c.fc = f64_consts[9]; c.a = f64_consts[10]; c.b = f64_consts[11]; c.eta_los = f64_consts[12];
-  c.eta_nlos = f64_consts[13]; c.safe_dist = f64_consts[14]; c.penalty = f64_consts[15]; c.rew_scale = f64_consts[16];
-  c.max_rate = f64_consts[17];
+  const EnvConsts c = env_consts(int_consts, f64_consts);
+  if (!obs_ubs && c.n != 1) return UAVGNN_EINVAL;   // one UBS: obs_ubs [B,1,0,3] holds nothing, its pointer may be null
   if (c.n < 1 || c.n > 16 || c.M < 1 || c.M > 1024 || c.R < 1 || c.R > 16 || c.A < 1) return UAVGNN_EUNSUPPORTED;
   const size_t lds = env_lds_bytes(c.n, c.M, c.R);
   if (lds > 64 * 1024) return UAVGNN_EUNSUPPORTED;

@@ -3,7 +3,7 @@
 // F = 2; 4 heads x 64 channels; math SURVEY Appendix A.1/A.3) write the two halves of one [N, 2H] row (the th.cat of
 // gnn_agents.py:106 never exists), with one constant-load prologue and one pass over the destination meta data.
 //
-// Round 4 layout (rounds 1-3: csrc/gatv2_hetero_pair.inc, still the fp32-MFMA build behind `phases` bit 8).  One workgroup of
+// Round 4 layout (rounds 1-3: csrc/gatv2_hetero_f32.hip, still the fp32-MFMA build behind `phases` bit 8).  One workgroup of
 // eight wavefronts per CU; every persistent wavefront runs two phases:
 //
 //  S  the `seen` relation of the destinations that HAVE in-edges, one destination at a time on 16-edge row tiles
@@ -36,6 +36,7 @@
 // the product): results equal the fp32-MFMA build's to fp32 rounding, not bit for bit.
 // Instantiated for D = 64 (H = 256: every BASELINE configuration); other shapes use the per-relation kernels.
 #include "common.h"
+#include "k1_wave.h"
 #include "k1_x3.h"
 
 namespace uavgnn {
@@ -63,33 +64,11 @@ constexpr int TPH = D / 16;        // channel tiles per head
 constexpr int FS_S = 4, FS_N = 2;
 constexpr int UB = 8;              // edge slots per pass of phase N
 constexpr int kBounceLd = 132;     // floats per destination row of the per-wave row buffer (128 + 4: 8 consecutive lanes of a ds_write_b128 on distinct 16-B slots)
-constexpr float kLog2e = 1.4426950408889634f;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-  return __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(v), CTRL, 0xf, 0xf, false));
-}
+// (f32x4, kLog2e, dpp_mov, row16_sum / row16_max, reduce_heads, rl: csrc/k1_wave.h)
 template <int CTRL>
 __device__ __forceinline__ int dpp_mov_i(int v) {
   return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false);
-}
-constexpr int kRowRor = 0x120;        // row_ror:n
-
-__device__ __forceinline__ float row16_sum(float v) {
-  v += dpp_mov<kRowRor + 8>(v);
-  v += dpp_mov<kRowRor + 4>(v);
-  v += dpp_mov<kRowRor + 2>(v);
-  v += dpp_mov<kRowRor + 1>(v);
-  return v;
-}
-__device__ __forceinline__ float row16_max(float v) {
-  v = fmaxf(v, dpp_mov<kRowRor + 8>(v));
-  v = fmaxf(v, dpp_mov<kRowRor + 4>(v));
-  v = fmaxf(v, dpp_mov<kRowRor + 2>(v));
-  v = fmaxf(v, dpp_mov<kRowRor + 1>(v));
-  return v;
 }
 __device__ __forceinline__ int row16_max_i(int v) {
   v = max(v, dpp_mov_i<kRowRor + 8>(v));
@@ -97,16 +76,6 @@ __device__ __forceinline__ int row16_max_i(int v) {
   v = max(v, dpp_mov_i<kRowRor + 2>(v));
   v = max(v, dpp_mov_i<kRowRor + 1>(v));
   return v;
-}
-
-// Sum pe[k] over the four 16-lane groups and leave head (lane>>4)'s total in every lane: 3 swaps + 3 adds.
-__device__ __forceinline__ float reduce_heads(float pe0, float pe1, float pe2, float pe3) {
-  auto s02 = __builtin_amdgcn_permlane32_swap(__float_as_uint(pe0), __float_as_uint(pe2), false, false);
-  const float a = __uint_as_float(s02[0]) + __uint_as_float(s02[1]);
-  auto s13 = __builtin_amdgcn_permlane32_swap(__float_as_uint(pe1), __float_as_uint(pe3), false, false);
-  const float b = __uint_as_float(s13[0]) + __uint_as_float(s13[1]);
-  auto t = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  return __uint_as_float(t[0]) + __uint_as_float(t[1]);
 }
 
 // 16-byte row-piece store under a wave-uniform 64-bit lane mask: EXEC is narrowed by scalar instructions around ONE
@@ -141,11 +110,6 @@ __device__ __forceinline__ void store_piece_all(float* base, unsigned lane_off, 
                : "v"(lane_off), "v"(v), "s"(base));
 }
 #define K1_TOUCH(x) asm volatile("" ::"v"(x))
-
-
-__device__ __forceinline__ float rl(float v, int lane) {
-  return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(v), lane));
-}
 
 struct RelParams {   // one GATv2Conv: fc_src, fc_dst, attn, res_fc (DGL layout, gnn_agents.py:93-96)
   const float* W_s; const float* b_s; const float* W_d; const float* b_d; const float* attn; const float* W_r;

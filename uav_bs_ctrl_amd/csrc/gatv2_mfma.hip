@@ -16,6 +16,7 @@
 //   input space (Appendix A.3 ii) and projected once per destination in the lane<->channel epilogue (coalesced row stores).
 // fp32 MFMA is bit-for-bit an fmaf chain (guide section 3), so numerics equal the VALU kernel's up to summation order.
 #include "common.h"
+#include "k1_wave.h"
 
 namespace uavgnn {
 namespace {
@@ -23,39 +24,6 @@ namespace {
 constexpr int kWavesPerBlock = 4;
 constexpr int kThreads = kWave * kWavesPerBlock;
 constexpr int NH = 4;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// All-reduce over the 16 lanes of a row (lane>>4 fixed) with DPP row rotations: v += ror(v, 8), 4, 2, 1.
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-  return __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(v), CTRL, 0xf, 0xf, false));
-}
-constexpr int kRowRor = 0x120;  // DPP control base of row_ror:n
-__device__ __forceinline__ float row16_sum(float v) {
-  v += dpp_mov<kRowRor + 8>(v);
-  v += dpp_mov<kRowRor + 4>(v);
-  v += dpp_mov<kRowRor + 2>(v);
-  v += dpp_mov<kRowRor + 1>(v);
-  return v;
-}
-__device__ __forceinline__ float row16_max(float v) {
-  v = fmaxf(v, dpp_mov<kRowRor + 8>(v));
-  v = fmaxf(v, dpp_mov<kRowRor + 4>(v));
-  v = fmaxf(v, dpp_mov<kRowRor + 2>(v));
-  v = fmaxf(v, dpp_mov<kRowRor + 1>(v));
-  return v;
-}
-
-// Sum pe[k] over the four 16-lane groups and leave head (lane>>4)'s total in every lane: 3 swaps + 3 adds.
-__device__ __forceinline__ float reduce_heads(float pe0, float pe1, float pe2, float pe3) {
-  auto s02 = __builtin_amdgcn_permlane32_swap(__float_as_uint(pe0), __float_as_uint(pe2), false, false);
-  const float a = __uint_as_float(s02[0]) + __uint_as_float(s02[1]);  // lo half: head 0 over {g,g+2}; hi half: head 2
-  auto s13 = __builtin_amdgcn_permlane32_swap(__float_as_uint(pe1), __float_as_uint(pe3), false, false);
-  const float b = __uint_as_float(s13[0]) + __uint_as_float(s13[1]);  // lo half: head 1; hi half: head 3
-  auto t = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  return __uint_as_float(t[0]) + __uint_as_float(t[1]);
-}
 
 template <int FS>
 __device__ __forceinline__ void load_xrow(const float* __restrict__ p, bool valid, float (&x)[FS]) {
@@ -72,8 +40,6 @@ __device__ __forceinline__ void load_xrow(const float* __restrict__ p, bool vali
     for (int f = 0; f < FS; ++f) x[f] = 0.f;
   }
 }
-
-constexpr float kLog2e = 1.4426950408889634f;
 
 // CHUNK selects how destinations are handed to the per-destination code:
 //   false - scalar loads of (id, offsets, x_v) one iteration ahead: best when every destination carries real work;

@@ -16,6 +16,7 @@
 // In-degrees above 8 are handled by further passes of 8 edges with an online softmax, so the kernel is correct for any
 // degree - the dispatcher only picks it when the mean in-degree is at most 8.
 #include "common.h"
+#include "k1_wave.h"   // kLog2e, dpp_mov, kRowRor, kQuadXor1
 
 namespace uavgnn {
 namespace {
@@ -24,14 +25,6 @@ constexpr int kWavesPerBlock = 4;
 constexpr int kThreads = kWave * kWavesPerBlock;
 constexpr int NH = 4;
 constexpr int kSlots = 8;          // edges per pass
-constexpr float kLog2e = 1.4426950408889634f;
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-  return __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(v), CTRL, 0xf, 0xf, false));
-}
-constexpr int kRowRor = 0x120;     // DPP control base of row_ror:n
-constexpr int kQuadXor1 = 0xB1;    // quad_perm:[1,0,3,2]
 
 // all-reduce over the 8 lanes of a 16-lane row that share this lane's parity (the 8 edge slots of one (head, half))
 __device__ __forceinline__ float slots_sum(float v) {

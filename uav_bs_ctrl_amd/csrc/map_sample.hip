@@ -39,6 +39,7 @@
 // argsort of the M keys, as a rank count - rank(m) = #{m' : key[m'] < key[m] or (key[m'] == key[m] and m' < m)}.  GT m of
 // the generation order lands in output row rank_shuffle(m); prior[rank_priority(m)] = m.
 #include "common.h"
+#include "env_math.h"   // Draws, unit, clip, stable_rank
 
 namespace uavgnn {
 namespace {
@@ -53,22 +54,6 @@ struct MapConsts {
   int kind, n, M, L_u, L_s, r, n_picks, gpg, origin;
   double range_pos, pitch_u, pitch_s, pitch_c, spread;
 };
-
-struct Draws {
-  uint32_t b, k0, k1, r0, r1;
-  __device__ __forceinline__ void words(uint32_t slot, uint32_t w[4]) const {
-    w[0] = b; w[1] = slot; w[2] = r0; w[3] = r1;
-    philox4x32_10(w, k0, k1);
-  }
-  __device__ __forceinline__ uint32_t word0(uint32_t slot) const {
-    uint32_t w[4];
-    words(slot, w);
-    return w[0];
-  }
-};
-
-__device__ __forceinline__ double unit(uint32_t w) { return (static_cast<double>(w >> 9) + 0.5) * 1.1920928955078125e-7; }
-__device__ __forceinline__ double clip(double v, double hi) { return fmin(fmax(v, 0.0), hi); }
 
 // Ordered sample of `count` distinct points of [0, C) by the whole wavefront.  pick[k] holds the word of draw k on entry and
 // the sampled point on return; key / val: the sparse table (position -> displaced value), at most `count` entries.
@@ -99,17 +84,6 @@ __device__ void sample_distinct(uint32_t* pick, int* key, int* val, int count, u
     if (j != k && at_j < 0) ++used;
     wave_sync();
   }
-}
-
-// stable rank of keys[m] among keys[0..M)
-__device__ __forceinline__ int stable_rank(const uint32_t* keys, int M, int m) {
-  const uint32_t km = keys[m];
-  int rank = 0;
-  for (int m2 = 0; m2 < M; ++m2) {
-    const uint32_t k2 = keys[m2];
-    rank += (k2 < km) || (k2 == km && m2 < m);
-  }
-  return rank;
 }
 
 __global__ __launch_bounds__(kThreads) void map_sample_kernel(MapConsts c, int B, int words_per_wave, int table,

@@ -8,14 +8,16 @@
 //   offsets        float64 difference / float64 min(range_pos, r_sns | r_comm), rounded to float32
 //   rates          float64(rate) / max_rate and float64(avg) / max_rate * M / (n R), rounded to float32
 //   state row      agent positions / range_pos in float64, GT positions / float(range_pos) in float32, the two rates as above
-// The expressions below are the text of that kernel (same contraction, no fast-math), so the bits are the same; the two rate columns
-// depend on the GT alone and are evaluated once per GT instead of once per (UBS, GT) pair - the same operations on the same operands.
+// Both kernels call the SAME functions for these elements (csrc/env_math.h; same contraction, no fast-math), so the bits are the same;
+// the two rate columns depend on the GT alone and are evaluated once per GT instead of once per (UBS, GT) pair - the same operations on
+// the same operands.
 //
 // One workgroup per (step t, sampled row b), grid-strided: it reads 16 n + 16 M bytes, keeps positions, the per-GT columns, the
 // visibility flags, the two offset columns of every (UBS, GT) pair and the UBS-UBS distances in LDS (9 n M + 16 M + ... bytes, at
 // most 64 KB), and writes n M Sg floats of obs_gt (plus the small fields).  The stores dominate, so every destination is written by FLATTENED element: consecutive lanes hold consecutive addresses, four elements per
 // lane as one 16-byte store where the field's floats per item are a multiple of four and its base is 16-byte aligned, else one float.
 #include "common.h"
+#include "env_math.h"
 
 namespace uavgnn {
 namespace {
@@ -27,7 +29,7 @@ constexpr int kThreads = 64;
 constexpr int kMaxGrid = 16384;      // 256 CUs x 32 resident wavefronts x 2; the rest is grid-strided
 
 struct RebuildArgs {
-  int n, M, R, fair_service, state_dim;
+  int n, M, R, fair_service, state_dim;                  // copied from the EnvConsts of uavgnn_env_step
   double range_pos, r_sns, r_comm, max_rate;
   const double* pos_ubs;             // [n_seq, T1, n, 2]
   const float* rate;                 // [n_seq, T1, M]
@@ -86,28 +88,27 @@ __global__ __launch_bounds__(kThreads) void replay_rebuild_kernel(RebuildArgs c)
     for (int k = tid; k < 2 * n; k += kThreads) PU[k] = pu[k];
     for (int k = tid; k < 2 * M; k += kThreads) PG[k] = pg[k];
     for (int m = tid; m < M; m += kThreads) {
-      RN[m] = static_cast<float>(static_cast<double>(rate[m]) / c.max_rate);
-      if (FAIR) AN[m] = static_cast<float>(static_cast<double>(avg[m]) / c.max_rate * M / (n * R));
+      RN[m] = obs_rate(rate[m], c.max_rate);
+      if (FAIR) AN[m] = obs_avg_rate(avg[m], c.max_rate, M, n, R);
     }
     __syncthreads();
     // distances as env_step_kernel's step 1: float64 norm of (float32 GT position - float64 UBS position), float32
     for (int k = tid; k < n * M; k += kThreads) {
       const int i = k / M, m = k - i * M;
       const double dx = static_cast<double>(PG[2 * m]) - PU[2 * i], dy = static_cast<double>(PG[2 * m + 1]) - PU[2 * i + 1];
-      const float d = static_cast<float>(sqrt(dx * dx + dy * dy));
+      const float d = dist_f32(dx, dy);
       const bool vis = d <= static_cast<float>(c.r_sns);
       VIS[k] = vis;
       // dx, dy ARE (float64(GT) - UBS): the two float64 divisions per pair run here, on full wavefronts, not once per stored element
-      OX[k] = vis ? static_cast<float>(dx / norm_s) : 0.f;
-      OY[k] = vis ? static_cast<float>(dy / norm_s) : 0.f;
+      OX[k] = vis ? obs_offset(dx, norm_s) : 0.f;
+      OY[k] = vis ? obs_offset(dy, norm_s) : 0.f;
     }
     for (int k = tid; k < n * n; k += kThreads) {
       const int i = k / n, jx = k - i * n;
       const double dx = PU[2 * jx] - PU[2 * i], dy = PU[2 * jx + 1] - PU[2 * i + 1];
-      const float d = static_cast<float>(sqrt(dx * dx + dy * dy));
-      DUU[k] = d;
+      DUU[k] = dist_f32(dx, dy);
     }
-    for (int k = tid; k < 2 * n; k += kThreads) AG[k] = static_cast<float>(PU[k] / c.range_pos);
+    for (int k = tid; k < 2 * n; k += kThreads) AG[k] = obs_pos(PU[k], c.range_pos);
     __syncthreads();
     // ---- observations (mubs_cov.py:215-242) ---------------------------------------------------------------------------------------
     write_flat(c.obs_gt + static_cast<size_t>(item) * n * M * Sg, n * M * Sg, c.vec_gt, [&](int e) -> float {
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(kThreads) void replay_rebuild_kernel(RebuildArgs c)
         const bool vis = DUU[i * n + other] <= static_cast<float>(c.r_comm);
         if (col == 0) return vis ? 1.f : 0.f;
         const int a = col - 1;
-        return vis ? static_cast<float>((PU[2 * other + a] - PU[2 * i + a]) / norm_c) : 0.f;
+        return vis ? obs_offset(PU[2 * other + a] - PU[2 * i + a], norm_c) : 0.f;
       });
     write_flat(c.obs_agent + static_cast<size_t>(item) * n * 2, 2 * n, c.vec_agent, [&](int e) -> float { return AG[e]; });
     if (c.d_u2u != nullptr)
@@ -139,7 +140,7 @@ __global__ __launch_bounds__(kThreads) void replay_rebuild_kernel(RebuildArgs c)
         if (e < 2 * n) return AG[e];
         const int q = e - 2 * n;
         const int m = q / Ss, col = q - m * Ss;
-        if (col <= 1) return PG[2 * m + col] / static_cast<float>(c.range_pos);
+        if (col <= 1) return state_gt_pos(PG[2 * m + col], c.range_pos);
         if (col == 2) return RN[m];
         return AN[m];
       });
@@ -162,7 +163,7 @@ inline int vec_ok(const float* p, long long floats_per_item) {
 
 using namespace uavgnn;
 
-// int_consts / f64_consts: the arrays of uavgnn_env_step (layout: csrc/env_sim.hip)
+// int_consts / f64_consts: the arrays of uavgnn_env_step (layout: include/uavgnn.h)
 extern "C" int uavgnn_replay_rebuild_obs(const int32_t* int_consts, const double* f64_consts, const double* pos_ubs,
                                          const float* rate, const float* avg, const float* pos_gts, int n_seq, int steps,
                                          const long long* idx, int B, float* obs_gt, int Sg, float* obs_ubs, float* obs_agent,
@@ -170,13 +171,13 @@ extern "C" int uavgnn_replay_rebuild_obs(const int32_t* int_consts, const double
   if (!int_consts || !f64_consts || !pos_ubs || !rate || !avg || !pos_gts || n_seq < 1 || steps < 1 || B < 0 ||
       (B > 0 && !idx) || !obs_gt || !obs_agent)
     return UAVGNN_EINVAL;
+  const EnvConsts ec = env_consts(int_consts, f64_consts);
   RebuildArgs c;
-  c.n = int_consts[0]; c.M = int_consts[1]; c.R = int_consts[2]; c.fair_service = int_consts[5];
-  c.range_pos = f64_consts[0]; c.r_sns = f64_consts[2]; c.r_comm = f64_consts[3]; c.max_rate = f64_consts[17];
+  c.n = ec.n; c.M = ec.M; c.R = ec.R; c.fair_service = ec.fair_service; c.state_dim = ec.state_dim;
+  c.range_pos = ec.range_pos; c.r_sns = ec.r_sns; c.r_comm = ec.r_comm; c.max_rate = ec.max_rate;
   if (Sg != (c.fair_service ? 5 : 4)) return UAVGNN_EINVAL;
   if (c.n < 1 || c.n > 16 || c.M < 1 || c.M > 1024 || c.R < 1 || c.R > 16) return UAVGNN_EUNSUPPORTED;
   if (c.n > 1 && !obs_ubs) return UAVGNN_EINVAL;
-  c.state_dim = uavgnn_env_state_dim(c.n, c.M, c.fair_service);
   c.pos_ubs = pos_ubs; c.rate = rate; c.avg = avg; c.pos_gts = pos_gts; c.idx = idx;
   c.n_seq = n_seq; c.T1 = steps; c.B = B;
   c.obs_gt = obs_gt; c.obs_ubs = obs_ubs; c.obs_agent = obs_agent; c.d_u2u = d_u2u; c.state = state;

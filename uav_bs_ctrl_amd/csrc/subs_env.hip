@@ -57,6 +57,7 @@
 // rank(m) = #{m' : key[m'] < key[m] or (key[m'] == key[m] and m' < m)}.  GT m of the generation order lands in output row
 // rank_shuffle(m); prior[rank_priority(m)] = m.
 #include "common.h"
+#include "env_math.h"
 
 namespace uavgnn {
 namespace {
@@ -112,8 +113,8 @@ __global__ __launch_bounds__(kWave * kMaxWavesPerBlock) void subs_env_step_kerne
     float d;
     if (moving) {
       const double dx = static_cast<double>(pg[2 * m]) - px, dy = static_cast<double>(pg[2 * m + 1]) - py;
-      d = static_cast<float>(sqrt(dx * dx + dy * dy));
-    } else {
+      d = dist_f32(dx, dy);
+    } else {   // reset time: float32 position, float32 arithmetic (not csrc/env_math.h's)
       const float dx = pg[2 * m] - pxf, dy = pg[2 * m + 1] - pyf;
       d = sqrtf(dx * dx + dy * dy);
     }
@@ -137,7 +138,7 @@ __global__ __launch_bounds__(kWave * kMaxWavesPerBlock) void subs_env_step_kerne
   }
   wave_sync();
   // ---- rates, averages, observations (:147-152, :159-171) -----------------------------------------------------------------------------
-  const double k_los = pow(10.0, c.eta_los / 20.0), k_nlos = pow(10.0, c.eta_nlos / 20.0);
+  const double k_los = a2g_excess_loss(c.eta_los), k_nlos = a2g_excess_loss(c.eta_nlos);
   const double noise = c.bw * c.n0;
   const size_t F = 2 + 4 * static_cast<size_t>(M);
   float* __restrict__ og = obs_gt + bM * 4;
@@ -146,14 +147,7 @@ __global__ __launch_bounds__(kWave * kMaxWavesPerBlock) void subs_env_step_kerne
   for (int m = lane; m < M; m += kWave) {
     const float d = AVG[m];
     const int served = SCH[m];
-    // A2G channel gain (envs/common.py:49-59)
-    const float ang = atanf(static_cast<float>(c.h_ubs) / (d + 1e-5f));
-    const float p_los = 1.f / (1.f + static_cast<float>(c.a) * expf(-static_cast<float>(c.b) * (ang - static_cast<float>(c.a))));
-    const double dd = sqrt(static_cast<double>(d * d) + c.h_ubs * c.h_ubs);
-    const double q = 4.0 * 3.141592653589793 * c.fc * dd / 3e8;
-    const double fspl = q * q;
-    const double pl = static_cast<double>(p_los) * fspl * k_los + static_cast<double>(1.f - p_los) * fspl * k_nlos;
-    const double p_rx = served ? c.p_tx * (1.0 / pl) : 0.0;
+    const double p_rx = served ? a2g_rx_power(c, d, k_los, k_nlos) : 0.0;   // A2G channel gain (envs/common.py:49-59)
     const double rate = c.bw * log2(1.0 + p_rx / noise) * 1e-6;
     const double avg = (static_cast<double>(avg_rate[bM + m]) * t + rate) / (t + 1);
     const double x = fmax(avg, 1e-6);                       // np.clip(x, 1e-6, inf) of the Jain index
@@ -203,40 +197,10 @@ __global__ __launch_bounds__(kWave * kMaxWavesPerBlock) void subs_env_step_kerne
   }
   wave_sync();
   // ---- next priorities (:157): STABLE ascending order of the stored averages ----------------------------------------------------------------
-  for (int m = lane; m < M; m += kWave) {
-    const float am = AVG[m];
-    int rank = 0;
-    for (int m2 = 0; m2 < M; ++m2) {
-      const float a2 = AVG[m2];
-      rank += (a2 < am) || (a2 == am && m2 < m);
-    }
-    prior[bM + rank] = m;
-  }
+  for (int m = lane; m < M; m += kWave) prior[bM + stable_rank(AVG, M, m)] = m;
 }
 
-// ---- reset-time sampler -------------------------------------------------------------------------------------------------------------
-struct Draws {
-  uint32_t b, k0, k1, r0, r1;
-  __device__ __forceinline__ void words(uint32_t slot, uint32_t w[4]) const {
-    w[0] = b; w[1] = slot; w[2] = r0; w[3] = r1;
-    philox4x32_10(w, k0, k1);
-  }
-};
-
-__device__ __forceinline__ double unit(uint32_t w) { return (static_cast<double>(w >> 9) + 0.5) * 1.1920928955078125e-7; }
-__device__ __forceinline__ double clip(double v, double hi) { return fmin(fmax(v, 0.0), hi); }
-
-// stable rank of keys[m] among keys[0..M)
-__device__ __forceinline__ int stable_rank(const uint32_t* keys, int M, int m) {
-  const uint32_t km = keys[m];
-  int rank = 0;
-  for (int m2 = 0; m2 < M; ++m2) {
-    const uint32_t k2 = keys[m2];
-    rank += (k2 < km) || (k2 == km && m2 < m);
-  }
-  return rank;
-}
-
+// ---- reset-time sampler (Draws, unit, clip, stable_rank: csrc/env_math.h) -------------------------------------------------------------
 __global__ __launch_bounds__(kWave * kMaxWavesPerBlock) void subs_env_sample_kernel(
     int G, int P, double range_pos, double r_cov, int B, const long long* __restrict__ rng, double* __restrict__ pos_ubs,
     float* __restrict__ pos_gts, int32_t* __restrict__ prior) {

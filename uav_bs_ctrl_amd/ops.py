@@ -13,8 +13,8 @@ from . import _lib as L
 NEG_SLOPE = 0.2  # DGL GATv2Conv default, not overridden at gnn_agents.py:93-96
 K1_IMAGE = os.environ.get("UAVGNN_K1_IMAGE", "1") != "0"   # prepared parameter image inside frozen_weights() scopes (A/B switch)
 HETERO_FUSED = True   # K1 forward of both encoder relations in one launch (csrc/gatv2_hetero.hip); False: per relation
-# K1's score GEMM on the bf16 matrix cores (exact three-way splits: fp32-level accuracy); False: the fp32-MFMA build of the same
-# kernel (csrc/gatv2_hetero_f32.hip) - the A/B reference and the K1 part of bench.py's strict-fp32 leg
+# K1's score GEMM on the bf16 matrix cores (exact three-way splits: fp32-level accuracy); False: the fp32-MFMA kernel of rounds 1-3
+# (csrc/gatv2_hetero_f32.hip, a source of its own) - the A/B reference and the K1 part of bench.py's strict-fp32 leg
 K1_BF16Z = os.environ.get("UAVGNN_K1_BF16Z", "1") != "0"
 # row maxima out of the time-batched K1 launches (more than K1_ROWMAX_MIN_ROWS destinations) for an f16x2 f_aggr forward (A/B switch)
 K1_ROWMAX = os.environ.get("UAVGNN_K1_ROWMAX", "1") != "0"

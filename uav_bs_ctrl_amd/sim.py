@@ -184,6 +184,7 @@ class BatchedUbsCoverageEnv:
         self.episode_limit = p.episode_limit
         a, b, eta_los, eta_nlos = p.chan()
         self.max_rate = p.max_rate if max_rate is None else float(max_rate)
+        # int_consts / f64_consts of uavgnn_env_step: layout in include/uavgnn.h
         self._ic = (ctypes.c_int32 * 7)(n, M, p.n_rbs, self.n_actions, p.episode_limit, int(p.fair_service),
                                         int(p.avoid_collision))
         self._fc = (ctypes.c_double * 18)(p.range_pos, p.r_cov, min(p.r_sns, 1e300), min(p.r_comm, 1e300), p.dt, p.h_ubs,
