@@ -328,6 +328,38 @@ int uavgnn_replay_sample_wide(const long long* state, long long* rng, int capaci
                               void* workspace, uavgnn_stream_t stream);
 int uavgnn_replay_gather(const long long* fields, int n_fields, const long long* idx, int B, uavgnn_stream_t stream);
 
+/* ---- prioritised sequence replay (csrc/replay_prio.hip; Schaul et al. ICLR'16, proportional variant, over sequences) ----------------
+ * prio: DEVICE uint32 [capacity], one FIXED-POINT priority per ring slot, 2^20 = 1.0; prio_max: DEVICE uint32 [1], the running maximum,
+ * initialised by the caller to 2^20.  state / rng / status as above; status bit 1: a priority update was skipped.  Every entry takes
+ * the stream, allocates nothing and never synchronises with the host; the number and grids of its launches depend on (capacity, B, T,
+ * C) only, never on the device-side size, so all of them capture into a hipGraph and replay with the CURRENT counters.  capacity <=
+ * 2^30 and B <= 65535, else UAVGNN_EUNSUPPORTED; null pointers, non-positive extents, NaN parameters: UAVGNN_EINVAL.
+ *
+ * _prio_commit: prio[(head + e) % capacity] = *prio_max for e < E.  Call it BEFORE uavgnn_replay_commit, which advances head.
+ * _prio_sample: stratified proportional sampling with replacement, integer arithmetic only in every decision.  THE RULE:
+ *   S = sum of prio[s] over s < size (64 bits; slots at or beyond size are never read into a decision).  With S = qB B + rB, stratum k
+ *   is [lo_k, hi_k), lo_k = k qB + (k rB) / B, hi_k = lo_{k+1}.  r_k = words 0 and 1 (low word first) of Philox4x32-10 at counter
+ *   (k, 1, draws_lo, draws_hi) under key (seed_lo, seed_hi); target_k = lo_k + (hi_k > lo_k ? r_k mod (hi_k - lo_k) : 0); idx[k] = the
+ *   slot s with prefix[s] <= target_k < prefix[s] + prio[s], prefix the exclusive prefix sum over s < size - ascending, repeats
+ *   possible.  weights[k] = (float) (w_k / max_j w_j) with w_k = pow((double) size * prio[idx[k]] / (double) S, -beta) in double.
+ *   Then draws += 1.  size == 0 (or S == 0): status |= 1, idx[k] = 0, weights[k] = 1, draws += 1.  1 <= B; 0 <= beta <= 16 (every
+ *   power stays finite in double), else UAVGNN_EINVAL.  Four launches (chunk sums
+ *   over one workgroup per 4096 slots of the CAPACITY, scan and targets, one wavefront per sample, weights).
+ *   workspace: DEVICE memory of _prio_workspace_bytes(capacity, B) bytes (0: an argument out of range), 16-byte aligned, owned by the
+ *   caller at a fixed address; the call does not depend on its contents at entry and carries nothing to the next call.
+ * _prio_update: td [T, B, C] float32 contiguous, idx [B] int64 ascending (a draw of _prio_sample).  For every b, in double:
+ *   a = eta max|td[:, b, :]| + (1 - eta) mean|td[:, b, :]|,  q = clamp(llrint(pow(a + eps, alpha) 2^20), 1, 2^32 - 1)  (alpha == 1:
+ *   a + eps itself), prio[idx[b]] = q, *prio_max = max(*prio_max, q).  Of a run of equal indices only the LAST row stores its q (every
+ *   valid row enters the maximum).  A non-finite a or an index outside [0, capacity) writes nothing and ORs status bit 1.  One launch;
+ *   B == 0: none. */
+long long uavgnn_replay_prio_workspace_bytes(int capacity, int B);   /* host only */
+int uavgnn_replay_prio_commit(const long long* state, int E, int capacity, uint32_t* prio, const uint32_t* prio_max,
+                              uavgnn_stream_t stream);
+int uavgnn_replay_prio_sample(const long long* state, long long* rng, int capacity, int B, const uint32_t* prio, double beta,
+                              long long* idx, float* weights, int32_t* status, void* workspace, uavgnn_stream_t stream);
+int uavgnn_replay_prio_update(const float* td, int T, int B, int C, const long long* idx, int capacity, double alpha, double eta,
+                              double eps, uint32_t* prio, uint32_t* prio_max, int32_t* status, uavgnn_stream_t stream);
+
 /* ---- compact replay ring: observations rebuilt from simulator state (csrc/replay_rebuild.hip) -----------------------
  * The padded observations and the global state of B sampled sequences, written TIME-MAJOR as the update's buffers hold them, from
  * the four arrays the multi-UBS simulator computes them from (reference: envs/mubs_cov/mubs_cov.py:212-297 get_obs / get_state; the

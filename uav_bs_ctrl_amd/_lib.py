@@ -103,6 +103,12 @@ SIGNATURES = {
     "uavgnn_replay_sample_wide_slots_per_workgroup": (_c_int, []),
     "uavgnn_replay_sample_wide": (_c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_int, _c_int, ctypes.c_void_p, _c_ip, ctypes.c_void_p, _c_st]),
     "uavgnn_replay_gather": (_c_int, [ctypes.POINTER(ctypes.c_longlong), _c_int, ctypes.c_void_p, _c_int, _c_st]),
+    "uavgnn_replay_prio_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int]),
+    "uavgnn_replay_prio_commit": (_c_int, [ctypes.c_void_p, _c_int, _c_int, ctypes.c_void_p, ctypes.c_void_p, _c_st]),
+    "uavgnn_replay_prio_sample": (_c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_int, _c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
+                                           _c_fp, _c_ip, ctypes.c_void_p, _c_st]),
+    "uavgnn_replay_prio_update": (_c_int, [_c_fp, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_int, ctypes.c_double, ctypes.c_double,
+                                           ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, _c_ip, _c_st]),
     "uavgnn_replay_rebuild_obs": (_c_int, [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double), _c_fp, _c_fp, _c_fp, _c_fp, _c_int,
                                            _c_int, ctypes.c_void_p, _c_int, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_fp, _c_st]),
     "uavgnn_colsum_acc": (_c_int, [_c_fp, ctypes.c_longlong, _c_int, _c_int, _c_fp, _c_int, _c_st]),

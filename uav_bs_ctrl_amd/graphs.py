@@ -317,6 +317,15 @@ class _GraphedUpdateBase:
     def _body(self) -> Dict:
         return self.learner.update(self._batch())
 
+    def _bind_weights(self, weights: Optional[th.Tensor], T: int, B: int, C: int) -> None:
+        """``weights`` [B] (None: the update is not prioritised) and the TD buffer ``td`` [T, B, C] the loss writes into."""
+        self.weights, self.td = weights, None
+        if weights is None:
+            return
+        if tuple(weights.shape) != (B,) or weights.dtype != th.float32 or not weights.is_contiguous() or weights.device != self.h0.device:
+            raise ValueError(f"weights: a contiguous float32 [{B}] tensor on the learner's device expected")
+        self.td = th.zeros(T, B, C, dtype=th.float32, device=weights.device)
+
     def load_from(self, replay, idx: th.Tensor) -> None:
         """The sequences ``idx`` of a device-state replay straight from its ring into the graph's buffers: ONE gather launch
         (``replay.gather_into``) instead of one ``index_select`` and one copy per field.  Same bits as ``load``."""
@@ -351,9 +360,11 @@ class GraphedUpdate(_GraphedUpdateBase):
     """
 
     def __init__(self, learner, B: int, T: int, n: int, M: int, r_comm: float = float("inf"), rew_dim: Optional[int] = None,
-                 warmup: int = 2, enc: str = "gnn", capture: bool = True):
+                 warmup: int = 2, enc: str = "gnn", capture: bool = True, weights: Optional[th.Tensor] = None):
         """capture=False: only the fixed-address buffers, ``_batch()`` and ``load`` / ``load_from`` - for a larger capture that holds the
-        update itself (``GraphedEpisode``)."""
+        update itself (``GraphedEpisode``).  weights: the fixed-address importance weights [B] of a prioritised replay (its
+        ``is_weights``, shared) - the batch then carries them and the loss leaves its TD errors in ``td`` [T, B, n] ([T, B, 1] with a
+        mixer); None: neither exists."""
         assert learner.fused_tail, "graph capture needs the device-resident update tail (CUDA learner)"
         self.learner, self.B, self.T, self.n, self.M, self.r_comm = learner, B, T, n, M, r_comm
         self._build = _builder(enc)      # enc='mlp': flattened-observation batches (exp2)
@@ -369,6 +380,7 @@ class GraphedUpdate(_GraphedUpdateBase):
         # QMIX (learner.py:145-148): the global state of all T+1 steps; None without a mixer (``SequenceReplay._gather_fields`` looks here)
         mixer = getattr(learner, "mixer", None)
         self.states = None if mixer is None else th.zeros(T + 1, B, mixer.state_dim, dtype=th.float32, device=dev)
+        self._bind_weights(weights, T, B, n if mixer is None else 1)
         if capture:
             self._capture_update(warmup)
 
@@ -385,6 +397,8 @@ class GraphedUpdate(_GraphedUpdateBase):
                    rews=self.rews, dones=self.dones)
         if self.states is not None:
             out["states"] = self.states
+        if self.weights is not None:
+            out.update(weights=self.weights, td_out=self.td)
         return out
 
     def load(self, m: Dict[str, th.Tensor]) -> None:
@@ -411,8 +425,10 @@ class GraphedSingleUbsUpdate(_GraphedUpdateBase):
 
     Data-parallel runs are cut at the gradient all-reduce exactly as ``GraphedUpdate`` is."""
 
-    def __init__(self, learner, B: int, T: int, M: int, enc: str = "gnn", warmup: int = 2, capture: bool = True):
-        """capture=False: only the fixed-address buffers, ``_batch()`` and ``load`` / ``load_from`` (see ``GraphedUpdate``)."""
+    def __init__(self, learner, B: int, T: int, M: int, enc: str = "gnn", warmup: int = 2, capture: bool = True,
+                 weights: Optional[th.Tensor] = None):
+        """capture=False: only the fixed-address buffers, ``_batch()`` and ``load`` / ``load_from``; weights: the importance weights [B] of
+        a prioritised replay, ``td`` [T, B, 1] then receives the TD errors (see ``GraphedUpdate``)."""
         self.learner, self.B, self.T, self.M, self.enc = learner, B, T, M, _single_ubs_enc(enc)
         dev, H = learner.device, learner.args.hidden_size
         f = dict(dtype=th.float32, device=dev)
@@ -421,12 +437,15 @@ class GraphedSingleUbsUpdate(_GraphedUpdateBase):
         self.h0, self.h1 = th.zeros(B, H, **f), th.zeros(B, H, **f)
         self.acts = th.zeros(T, B, 1, dtype=th.int64, device=dev)
         self.rews, self.dones = th.zeros(T, B, 1, **f), th.zeros(T, B, 1, **f)
+        self._bind_weights(weights, T, B, 1)
         if capture:
             self._capture_update(warmup)
 
     def _batch(self) -> Dict:
         T, B, M = self.T, self.B, self.M
         out = dict(h0=self.h0, h1=self.h1, acts=self.acts, rews=self.rews, dones=self.dones)
+        if self.weights is not None:
+            out.update(weights=self.weights, td_out=self.td)
         if self.enc == "gnn":
             gt, agent = self.gt, self.agent
             out["obs"] = [from_single_ubs_obs(gt[t], agent[t]) for t in range(T + 1)]
@@ -536,6 +555,11 @@ class Episode(_EnvObs):
     replay: a ``replay.CompactSequenceReplay`` (built ``for_env(env, ...)``) instead stages ``env.replay_state()`` and the hidden state at
     every step and rebuilds observations and the mixer's state in its gather; it needs no stored ``state``, only ``rew_dim=1`` under QMIX.
 
+    replay: built with ``prioritized=(alpha, beta, eta, eps)`` - every update is draw (proportional to priority), gather, ``learner.update``
+    on a batch that carries the draw's importance weights (``replay.is_weights``, shared with the update's buffer: no copy), then
+    ``replay.update_priorities(idx, upd.td)`` with the TD errors the loss left - after ``apply``, so with ``updates_per_segment > 1`` the
+    next draw already sees the new priorities.
+
     stats: a ``stats.EpochStats`` holding the info keys (EpRet, EpLen, AvgGlobalUtility, TotalThroughput, FairIdx, and ProbCollision for
     the multi-UBS simulator) and, when ``train``, LossQ: the body pushes the info tensors once at the end of the episode and LossQ after
     every update (run.py:93, :99) - launches on fixed addresses, so they replay with the graph.  None: nothing is pushed.
@@ -569,8 +593,12 @@ class Episode(_EnvObs):
         dev = learner.device
         self._bind_env(learner, env, enc)
         self.compact = False
+        # a prioritised ring: the update reads the draw's importance weights where the sampler leaves them (one tensor, no copy)
+        self.prioritized = getattr(replay, "prioritized", None) is not None
+        weights = replay.reserve_batch(self.batch_size) if self.prioritized and self.train else None
         if self.single:
-            self.upd = GraphedSingleUbsUpdate(learner, self.batch_size, self.T, env.n_gts, enc, capture=False) if self.train else None
+            self.upd = GraphedSingleUbsUpdate(learner, self.batch_size, self.T, env.n_gts, enc, capture=False,
+                                              weights=weights) if self.train else None
         else:
             from .replay import CompactSequenceReplay
             # a compact ring stores the simulator's state, not its observations: nothing of `state` is staged, the gather rebuilds it
@@ -585,7 +613,7 @@ class Episode(_EnvObs):
                     raise ValueError(f"replay: the mixer's q_tot is one value per environment (share_reward) but the replay stores "
                                      f"rew_dim = {rd}")
             self.upd = GraphedUpdate(learner, self.batch_size, self.T, env.n_agents, env.n_gts, env.p.r_comm,
-                                     replay.mem["rew"].shape[-1], enc=enc, capture=False) if self.train else None
+                                     replay.mem["rew"].shape[-1], enc=enc, capture=False, weights=weights) if self.train else None
         # built here, outside any capture: init_hidden moves a CPU row to the device, the scalars below are host-to-device copies
         self.h_zero = learner.init_hidden(self.E)
         self.eps = th.full((1,), self.eps_start, dtype=th.float32, device=dev)
@@ -646,6 +674,8 @@ class Episode(_EnvObs):
                     self.idx = rb.sample_indices(self.batch_size)
                     rb.gather_into(self.idx, self.upd)
                     out = self._update(self.upd._batch())
+                    if self.prioritized:          # after `apply`: the next draw of this segment already sees the new priorities
+                        rb.update_priorities(self.idx, self.upd.td)
                     if self.stats is not None:
                         self.stats.push(LossQ=out["LossQ"])
         if self.stats is not None:
@@ -693,6 +723,8 @@ class GraphedEpisode(Episode):
         state = [replay.state, replay.rng, replay.status, self.t, self.eps, env.reset_rng]
         if self.explore is not None:
             state.append(self.explore)
+        if self.prioritized:                           # the warm-up's commits and priority updates are undone as well
+            state += [replay.prio, replay.prio_max]
         if stats is not None:
             state += stats.state_tensors()             # the warm-up episodes' pushes are undone as well
         # flush: as GraphedCycle (the body's stores are its own, so nothing of the learner's store is read); sync: whenever the learner

@@ -308,7 +308,23 @@ class MultiAgentQLearner:
             next_vals = self.target_mixer(next_vals, batch["states"][1:])
         rews, dones = batch["rews"].expand_as(next_vals), batch["dones"].expand_as(next_vals)
         target = rews + self.gamma * (1 - dones) * next_vals
-        return _mse(qvals, target), agent_out, target_out
+        weights = batch.get("weights")
+        if weights is None:
+            return _mse(qvals, target), agent_out, target_out
+        # prioritised replay: importance weights [B] of the sampled sequences in the loss, and the chunk's TD errors kept for the
+        # priority update (``last_td``: one [T, B, C] tensor per chunk of the update; ``batch["td_out"]``: a fixed-address buffer of a
+        # captured update that receives them instead of a fresh tensor)
+        d = qvals - target
+        td = d.detach()
+        if batch.get("td_out") is not None:
+            td = batch["td_out"].copy_(td)
+        td = td if td.is_contiguous() else td.contiguous()
+        chunks = getattr(self, "_td_chunks", None)
+        if chunks is None:                               # `loss` called on its own: the TD errors of this call alone
+            self.last_td = [td]
+        else:                                            # inside `accumulate`: one entry per chunk
+            chunks.append(td)
+        return _weighted_mse(d, weights), agent_out, target_out
 
     def update(self, batch) -> Dict:
         """One gradient step = ``accumulate`` (loss + backward into the flat gradient buffer) -> the ONE collective of the
@@ -340,6 +356,11 @@ class MultiAgentQLearner:
         if len(sizes) > 1:      # the mean of chunk means is the mean over all sequences only for equally sized chunks
             raise ValueError(f"accumulate: chunks of different sizes {sorted(sizes)}")
         self.grads.zero_()
+        weighted = {"weights" in b for b in chunks}
+        if len(weighted) > 1:
+            raise ValueError("accumulate: some chunks carry importance weights and some do not")
+        self.__dict__.pop("last_td", None)
+        self._td_chunks = [] if True in weighted else None     # prioritised replay: `_td_loss` appends one [T, B, C] tensor per chunk
         # weight gradients of the fused recurrent step are accumulated in place across the T+1 steps (and across the
         # chunks) and folded into the flat gradient buffer once (ops.WeightGradSink); everything else reaches it through
         # autograd
@@ -359,6 +380,8 @@ class MultiAgentQLearner:
                 sink.flush()
         finally:
             ops.GRAD_SINK = None
+            if self._td_chunks is not None:
+                self.last_td, self._td_chunks = self._td_chunks, None
         return dict(LossQ=loss, QVals=agent_out.detach())      # QVals: the LAST chunk's (LossQ: the mean over all chunks)
 
     def invalidate_weight_cache(self) -> None:
@@ -491,6 +514,20 @@ def _mse(x: th.Tensor, y: th.Tensor) -> th.Tensor:
     while S < 1024 and n % (2 * S) == 0 and n // (2 * S) >= 256:
         S *= 2
     return d.square().view(S, n // S).sum(1).sum() / n
+
+
+def _weighted_mse(d: th.Tensor, w: th.Tensor) -> th.Tensor:
+    """sum_b w[b] d[t, b, c]^2 / (T B C) for d [T, B, C] and w [B], in the two stages of ``_mse`` (row sums, then their sum: no
+    semaphore reduction, no atomically accumulated scalar)."""
+    T, B, C = d.shape
+    x = d.square() * w.view(1, B, 1)
+    n = x.numel()
+    if n == 0:
+        return x.sum()
+    S = 1
+    while S < 1024 and n % (2 * S) == 0 and n // (2 * S) >= 256:
+        S *= 2
+    return x.reshape(S, n // S).sum(1).sum() / n
 
 
 def params_checksum(module: th.nn.Module) -> th.Tensor:

@@ -32,6 +32,23 @@ from .graph import HeteroBatch, from_obs_dicts, from_padded_obs, from_padded_obs
 SCHEME = ("gt", "ubs", "agent", "d_u2u", "h", "state", "act", "rew", "done")
 NARROW_SAMPLER_CAPACITY = 65536      # uavgnn_replay_sample: one workgroup, one launch; above it uavgnn_replay_sample_wide
 MAX_DEVICE_CAPACITY = 2 ** 30        # the limit of uavgnn_replay_sample_wide
+PRIO_ONE = 1 << 20                   # the fixed-point 1.0 of a priority (csrc/replay_prio.hip)
+
+
+def _check_prioritized(prioritized, device_state: bool):
+    """None, or (alpha, beta, eta, eps) as four floats: explicit numbers - the package keeps no defaults."""
+    if prioritized is None:
+        return None
+    if not device_state:
+        raise ValueError("prioritized: priorities live on the device (device_state=True); a host-state ring has none")
+    try:
+        alpha, beta, eta, eps = (float(v) for v in prioritized)
+    except (TypeError, ValueError):
+        raise ValueError(f"prioritized: None or four numbers (alpha, beta, eta, eps) expected, got {prioritized!r}") from None
+    if not (alpha >= 0.0 and 0.0 <= beta <= 16.0 and 0.0 <= eta <= 1.0 and eps >= 0.0) or float("inf") in (alpha, eps):
+        raise ValueError(f"prioritized = (alpha, beta, eta, eps) = {(alpha, beta, eta, eps)}: finite alpha, eps >= 0, beta in [0, 16] "
+                         f"(the sampler's weights stay finite) and eta in [0, 1] expected")
+    return alpha, beta, eta, eps
 
 
 class _RingState:
@@ -39,6 +56,11 @@ class _RingState:
     ``device_state=True``: ``state`` int64 {head, size}, ``rng`` int64 {seed, draws} and ``status`` int32 [1] are DEVICE tensors; the
     commit, the sampler and the gather into a captured update's buffers are one launch each (csrc/replay.hip) that read the
     counters on the device - so a hipGraph holding them replays with the CURRENT ring position (``graphs.GraphedEpisode``).
+    ``prioritized=(alpha, beta, eta, eps)`` (opt-in, device state only; None - the default - leaves every launch as it was): proportional
+    prioritised replay over sequences (csrc/replay_prio.hip).  ``prio`` [capacity] / ``prio_max`` [1] hold unsigned 32-bit FIXED-POINT
+    priorities (2^20 = 1.0) as the bits of int32 tensors; a commit gives the new sequences ``prio_max``, ``sample_indices`` draws
+    stratified and proportional WITH replacement (ascending slots, repeats possible) and leaves the importance weights in
+    ``is_weights`` [B], ``update_priorities(idx, td)`` rewrites the priorities of a batch from its TD errors.
     A class sets ``_scheme`` (its field names: ``_obs_fields``, the observation side of a transition, then act / rew / done) and
     ``mem`` / ``cur`` / ``capacity`` / ``T`` / ``n_envs`` / ``device`` before ``_init_ring_state``."""
 
@@ -64,8 +86,10 @@ class _RingState:
             if k in tr:
                 self.cur[k][:, self.ptr] = tr[k]
 
-    def _check_device_state(self, device_state: bool) -> None:
-        """What ``device_state=True`` asks of ``device`` / ``n_envs`` / ``capacity`` - a constructor calls it BEFORE it allocates the ring."""
+    def _check_device_state(self, device_state: bool, prioritized=None) -> None:
+        """What ``device_state=True`` asks of ``device`` / ``n_envs`` / ``capacity``, and ``prioritized`` of ``device_state`` - a constructor
+        calls it BEFORE it allocates the ring."""
+        self.prioritized = _check_prioritized(prioritized, bool(device_state))
         if not device_state:
             return
         if self.device.type != "cuda":
@@ -76,7 +100,7 @@ class _RingState:
             raise ValueError(f"device_state=True: capacity = {self.capacity} exceeds the device sampler's limit of 2^30 = "
                              f"{MAX_DEVICE_CAPACITY} sequences")
 
-    def _init_ring_state(self, device_state: bool, seed: Optional[int]) -> None:
+    def _init_ring_state(self, device_state: bool, seed: Optional[int], is_weights: Optional[th.Tensor] = None) -> None:
         self.device_state = bool(device_state)
         self.ptr = 0            # time index inside the sequences under construction (buffer.py:16)
         self.head = 0           # next ring slot
@@ -85,7 +109,7 @@ class _RingState:
             if seed is not None:
                 raise ValueError("seed: the key of the device sampler (device_state=True); the host sampler takes generator=")
             return
-        self._check_device_state(True)
+        self._check_device_state(True, self.prioritized)
         if seed is None:       # from torch's default generator: torch.manual_seed reproduces a run
             seed = int(th.randint(0, 2 ** 62, (1,)).item())
         self.head = self.size = None                          # the counters are ``state`` on the device
@@ -103,6 +127,38 @@ class _RingState:
             if src.numel() > 0:
                 rows += [src.data_ptr(), dst.data_ptr(), src[0].numel() * src.element_size()]
         self._commit_fields = (ctypes.c_longlong * len(rows))(*rows)
+        if self.prioritized is not None:
+            self._init_priorities(is_weights)
+
+    def _init_priorities(self, is_weights: Optional[th.Tensor]) -> None:
+        """``prioritized=(alpha, beta, eta, eps)``: one fixed-point priority per ring slot (uint32 bits in an int32 tensor; ``PRIO_ONE`` =
+        2^20 = 1.0), the running maximum new sequences are committed with, and - per batch size, at fixed addresses, so a captured draw
+        replays on them - the sampler's scratch and the importance weights ``is_weights`` [B] of the LAST draw."""
+        self.prio = th.full((self.capacity,), PRIO_ONE, dtype=th.int32, device=self.device)
+        self.prio_max = th.full((1,), PRIO_ONE, dtype=th.int32, device=self.device)
+        self.is_weights, self._prio_ws, self._prio_batch = None, None, None
+        if is_weights is not None:
+            if is_weights.dim() != 1 or is_weights.dtype != th.float32 or not is_weights.is_contiguous() or is_weights.device != self.prio.device:
+                raise ValueError("is_weights: a contiguous float32 [B] tensor on the ring's device expected")
+            self._prio_buffers(is_weights.numel(), is_weights)
+
+    def reserve_batch(self, batch_size: int) -> th.Tensor:
+        """``is_weights`` for draws of ``batch_size`` sequences, allocated now if no draw has fixed it yet - what a captured update binds."""
+        if self.prioritized is None:
+            raise ValueError("reserve_batch needs prioritized=(alpha, beta, eta, eps)")
+        if self._prio_batch is None:
+            self._prio_buffers(int(batch_size))
+        if int(batch_size) != self._prio_batch:
+            raise ValueError(f"prioritized: is_weights holds {self._prio_batch} weights, a batch of {batch_size} was asked for")
+        return self.is_weights
+
+    def _prio_buffers(self, B: int, is_weights: Optional[th.Tensor] = None) -> None:
+        n = L.lib().uavgnn_replay_prio_workspace_bytes(self.capacity, B)
+        if n <= 0:
+            raise ValueError(f"prioritized: a batch of {B} sequences is outside the sampler's range [1, 65535]")
+        self._prio_ws = th.empty(n, dtype=th.uint8, device=self.device)
+        self.is_weights = th.ones(B, dtype=th.float32, device=self.device) if is_weights is None else is_weights
+        self._prio_batch = B
 
     def __len__(self) -> int:
         """Committed sequences.  device_state=True: reads ``state`` from the device - a host SYNCHRONISATION (never inside a capture)."""
@@ -112,6 +168,9 @@ class _RingState:
         """The E sequences under construction -> ring slots (head + e) % capacity; head and size advance (buffer.py:31)."""
         E = self.n_envs
         if self.device_state:
+            if self.prioritized is not None:          # first: it reads `head`, which the commit's second launch advances
+                L.check(L.lib().uavgnn_replay_prio_commit(self.state.data_ptr(), E, self.capacity, self.prio.data_ptr(),
+                                                          self.prio_max.data_ptr(), L.stream()), "uavgnn_replay_prio_commit")
             L.check(L.lib().uavgnn_replay_commit(self._commit_fields, len(self._commit_fields) // 3, E, self.capacity,
                                                  self.state.data_ptr(), L.stream()), "uavgnn_replay_commit")
             return
@@ -130,6 +189,8 @@ class _RingState:
             if generator is not None:
                 raise ValueError("device_state=True: the sampler is keyed by the device `rng` pair, not by a torch generator")
             idx = th.empty(batch_size, dtype=th.int64, device=self.device)
+            if self.prioritized is not None:
+                return self._sample_prioritized(idx)
             if self._sample_ws is not None:
                 L.check(L.lib().uavgnn_replay_sample_wide(self.state.data_ptr(), self.rng.data_ptr(), self.capacity, batch_size,
                                                           idx.data_ptr(), self.status.data_ptr(), self._sample_ws.data_ptr(), L.stream()),
@@ -141,11 +202,41 @@ class _RingState:
         assert self.size >= batch_size, "Insufficient samples for update."
         return th.randperm(self.size, generator=generator, device=self.device)[:batch_size]
 
+    def _sample_prioritized(self, idx: th.Tensor) -> th.Tensor:
+        """Stratified proportional draw WITH replacement (uavgnn_replay_prio_sample, four launches): ascending slots, repeats possible;
+        the importance weights of the draw, normalised by their maximum, are left in ``is_weights`` (one buffer per ring: the first
+        draw fixes the batch size unless the constructor was given the buffer)."""
+        B = idx.numel()
+        self.reserve_batch(B)
+        L.check(L.lib().uavgnn_replay_prio_sample(self.state.data_ptr(), self.rng.data_ptr(), self.capacity, B, self.prio.data_ptr(),
+                                                  float(self.prioritized[1]), idx.data_ptr(), self.is_weights.data_ptr(),
+                                                  self.status.data_ptr(), self._prio_ws.data_ptr(), L.stream()), "uavgnn_replay_prio_sample")
+        return idx
+
+    def update_priorities(self, idx: th.Tensor, td: th.Tensor) -> None:
+        """New priorities of the sampled sequences ``idx`` [B] (ascending, as drawn) from the TD errors ``td`` [T, B, C] of the update formed
+        on them: eta max|td| + (1 - eta) mean|td| per sequence, (. + eps)^alpha in fixed point; ``prio_max`` grows with them.  One launch
+        (uavgnn_replay_prio_update); a non-finite row is skipped and sets status bit 1 (``check()``)."""
+        if self.prioritized is None:
+            raise ValueError("update_priorities needs prioritized=(alpha, beta, eta, eps)")
+        if idx.dtype != th.int64 or not idx.is_contiguous():
+            raise ValueError("idx: a contiguous int64 tensor expected")
+        if td.dim() != 3 or td.shape[1] != idx.numel() or td.dtype != th.float32 or not td.is_contiguous():
+            raise ValueError(f"td: a contiguous float32 [T, {idx.numel()}, C] tensor expected, got {tuple(td.shape)} {td.dtype}")
+        L.require_gpu(idx, td)
+        alpha, _, eta, eps = self.prioritized
+        T, B, C = td.shape
+        L.check(L.lib().uavgnn_replay_prio_update(td.data_ptr(), T, B, C, idx.data_ptr(), self.capacity, alpha, eta, eps,
+                                                  self.prio.data_ptr(), self.prio_max.data_ptr(), self.status.data_ptr(), L.stream()),
+                "uavgnn_replay_prio_update")
+
     def check(self) -> None:
         """Raises when a kernel of the device-resident path flagged an error (a host synchronisation)."""
         if self.device_state and int(self.status.item()) != 0:
             raise L.UavGnnError(f"replay status = {int(self.status.item()):#x}: bit 0 - a batch larger than the number of committed "
-                                f"sequences was sampled (its indices were wrapped into the ring)")
+                                f"sequences was sampled (its indices were wrapped into the ring)"
+                                + ("; bit 1 - a priority update was skipped (non-finite TD errors, or an index outside the ring)"
+                                   if self.prioritized is not None else ""))
 
     def _gather_fields(self, target, B: int):
         """[(ring tensor, first step, destination, steps)] of ``gather_into``: a class lists what its update buffers hold."""
@@ -181,11 +272,12 @@ class SequenceReplay(_RingState):
 
     def __init__(self, capacity: int, max_seq_len: int, n_agents: int, n_gts: int, hidden_size: int,
                  n_envs: int = 1, state_dim: int = 0, r_comm: float = float("inf"), rew_dim: Optional[int] = None,
-                 device="cuda", device_state: bool = False, seed: Optional[int] = None):
+                 device="cuda", device_state: bool = False, seed: Optional[int] = None, prioritized=None,
+                 is_weights: Optional[th.Tensor] = None):
         T, n, M = max_seq_len, n_agents, n_gts
         self.capacity, self.T, self.n, self.M, self.n_envs = capacity, T, n, M, n_envs
         self.r_comm, self.device = r_comm, th.device(device)
-        self._check_device_state(device_state)
+        self._check_device_state(device_state, prioritized)
         f = dict(dtype=th.float32, device=self.device)
         rd = n if rew_dim is None else rew_dim
 
@@ -197,7 +289,7 @@ class SequenceReplay(_RingState):
                         done=th.zeros(lead, T, 1, **f))
         self.mem = ring(capacity)
         self.cur = ring(n_envs)
-        self._init_ring_state(device_state, seed)
+        self._init_ring_state(device_state, seed, is_weights)
 
     def _gather_fields(self, target, B: int):
         m, o, T = self.mem, target.obs, self.T
@@ -282,7 +374,7 @@ class CompactSequenceReplay(_RingState):
     step_fields = ("pos_ubs", "rate", "avg", "pos_gts")      # what ``learner.cache`` takes from ``obs`` / ``next_obs``
 
     def __init__(self, env, capacity: int, max_seq_len: int, hidden_size: int, rew_dim: Optional[int] = None,
-                 device_state: bool = True, seed: Optional[int] = None):
+                 device_state: bool = True, seed: Optional[int] = None, prioritized=None, is_weights: Optional[th.Tensor] = None):
         if not device_state:
             raise ValueError("CompactSequenceReplay: device_state=True only (the rebuild is a device launch; no host path exists)")
         T, n, M = max_seq_len, env.n_agents, env.n_gts
@@ -290,7 +382,7 @@ class CompactSequenceReplay(_RingState):
         self.r_comm, self.device = env.p.r_comm, th.device(env.device)
         if self.device.type != "cuda":
             raise ValueError("CompactSequenceReplay: the ring, its counters and the rebuild live on the GPU (no CPU fallback exists)")
-        self._check_device_state(True)
+        self._check_device_state(True, prioritized)
         self._ic, self._fc = env._ic, env._fc                # the constant arrays uavgnn_env_step takes
         self.Sg, self.state_dim, self.hidden_size = env.out["obs_gt"].shape[-1], env.state_dim, hidden_size
         self.rew_dim = n if rew_dim is None else rew_dim
@@ -303,11 +395,12 @@ class CompactSequenceReplay(_RingState):
                         done=th.zeros(lead, T, 1, **f))
         self.mem = ring(capacity)
         self.cur = ring(self.n_envs)
-        self._init_ring_state(True, seed)
+        self._init_ring_state(True, seed, is_weights)
 
     @classmethod
-    def for_env(cls, env, capacity: int, max_seq_len: int, hidden_size: int, rew_dim: Optional[int] = None, seed: Optional[int] = None):
-        return cls(env, capacity, max_seq_len, hidden_size, rew_dim, True, seed)
+    def for_env(cls, env, capacity: int, max_seq_len: int, hidden_size: int, rew_dim: Optional[int] = None, seed: Optional[int] = None,
+                prioritized=None, is_weights: Optional[th.Tensor] = None):
+        return cls(env, capacity, max_seq_len, hidden_size, rew_dim, True, seed, prioritized, is_weights)
 
     @property
     def bytes_per_sequence(self) -> int:
@@ -398,11 +491,11 @@ class SingleUbsSequenceReplay(_RingState):
     _scheme, _obs_fields = SINGLE_UBS_SCHEME, ("gt", "agent", "h")
 
     def __init__(self, capacity: int, max_seq_len: int, n_gts: int, hidden_size: int, n_envs: int = 1, device="cuda",
-                 device_state: bool = False, seed: Optional[int] = None):
+                 device_state: bool = False, seed: Optional[int] = None, prioritized=None, is_weights: Optional[th.Tensor] = None):
         T, M = max_seq_len, n_gts
         self.capacity, self.T, self.M, self.n_envs = capacity, T, M, n_envs
         self.device = th.device(device)
-        self._check_device_state(device_state)
+        self._check_device_state(device_state, prioritized)
         f = dict(dtype=th.float32, device=self.device)
 
         def ring(lead):  # committed sequences / sequences under construction (one per parallel env)
@@ -411,7 +504,7 @@ class SingleUbsSequenceReplay(_RingState):
                         rew=th.zeros(lead, T, 1, **f), done=th.zeros(lead, T, 1, **f))
         self.mem = ring(capacity)
         self.cur = ring(n_envs)
-        self._init_ring_state(device_state, seed)
+        self._init_ring_state(device_state, seed, is_weights)
 
     def _gather_fields(self, target, B: int):
         m, T = self.mem, self.T

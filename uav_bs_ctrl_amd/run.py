@@ -4,7 +4,8 @@ log rows, checkpoints, trajectory films and resume.
     run = Run.create(exp="exp3", env="8ubs", args=args, output_dir="data/exp3_8ubs_s0", seed=0, n_envs=32)
     run.train()                          # all remaining epochs; run.train(epochs=k): k more
     run = Run.resume("data/exp3_8ubs_s0")    # rebuilds everything from config.json + state.pt and goes on, bit for bit
-    python -m uav_bs_ctrl_amd.run --exp exp3 --env 8ubs --args-json args.json --out data/exp3_8ubs_s0 [--seed 0 --envs 32 --resume --eager --compact-replay]
+    python -m uav_bs_ctrl_amd.run --exp exp3 --env 8ubs --args-json args.json --out data/exp3_8ubs_s0 [--seed 0 --envs 32 --resume --eager --compact-replay
+                                  --prioritized ALPHA BETA ETA EPS]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N -m uav_bs_ctrl_amd.run ...     # data-parallel: N ranks, one GPU each
 
 This is host orchestration over launches that exist: a collect-only and a training ``graphs.GraphedEpisode``, one
@@ -305,16 +306,32 @@ def _reference_env(exp: str, env) -> tuple:
 
 def run_config(exp: str, env, ns, seed: int = 0, n_envs: int = 32, n_test_envs: Optional[int] = None, updates_per_segment: int = 1,
                graphed: bool = True, save_replay: bool = True, world: int = 1, force_collective: bool = False,
-               compact_replay: bool = False) -> dict:
+               compact_replay: bool = False, prioritized=None) -> dict:
     """The ``uav_bs_ctrl_amd`` entry of ``config.json``: everything of ``Run.create``'s arguments that ``Run.resume`` needs to rebuild the
-    same run (host only).  compact_replay with exp1 is a ``ValueError``: the single-UBS observations are M x 4 floats already."""
+    same run (host only).  compact_replay with exp1 is a ``ValueError``: the single-UBS observations are M x 4 floats already.
+    prioritized: None, or (alpha, beta, eta, eps) - the key ``prioritized`` enters the entry ONLY when set (absent means off, so a
+    directory written before the option existed resumes unchanged)."""
     if compact_replay and exp == "exp1":
         raise ValueError("compact_replay: the compact ring stores the multi-UBS simulator's state (exp2 / exp3); exp1's observations "
                          "are already n_gts x 4 floats per step")
-    return dict(exp=exp, env=_env_to_config(exp, env), n_envs=int(n_envs),
-                n_test_envs=int(ns.num_test_episodes if n_test_envs is None else n_test_envs),
-                updates_per_segment=int(updates_per_segment), graphed=bool(graphed), save_replay=bool(save_replay),
-                seeds=derive_seeds(seed), world=int(world), force_collective=bool(force_collective), compact_replay=bool(compact_replay))
+    out = dict(exp=exp, env=_env_to_config(exp, env), n_envs=int(n_envs),
+               n_test_envs=int(ns.num_test_episodes if n_test_envs is None else n_test_envs),
+               updates_per_segment=int(updates_per_segment), graphed=bool(graphed), save_replay=bool(save_replay),
+               seeds=derive_seeds(seed), world=int(world), force_collective=bool(force_collective), compact_replay=bool(compact_replay))
+    if prioritized is not None:
+        out["prioritized"] = _prioritized(prioritized)
+    return out
+
+
+def _prioritized(values) -> list:
+    """[alpha, beta, eta, eps] as floats (the ring's constructor checks their ranges)."""
+    try:
+        out = [float(v) for v in values]
+    except (TypeError, ValueError):
+        out = []
+    if len(out) != 4:
+        raise ValueError(f"prioritized: None or four numbers (alpha, beta, eta, eps) expected, got {values!r}")
+    return out
 
 
 # ---- the driver -------------------------------------------------------------------------------------------------------------------------
@@ -359,6 +376,8 @@ class Run:
         self.compact_replay = bool(ours.get("compact_replay", False))     # absent in a config.json written before the option existed
         if self.compact_replay and self.single:
             raise ValueError("compact_replay: the compact ring stores the multi-UBS simulator's state (exp2 / exp3), not exp1's")
+        # absent in a config.json written without the option: the uniform sampler, no priority tensors
+        self.prioritized = tuple(_prioritized(ours["prioritized"])) if ours.get("prioritized") is not None else None
         if getattr(args, "mixer", False):
             raise ValueError("mixer = True is not covered by the driver yet: graphs.Episode / GraphedEpisode train with a mixer, "
                              "Run does not build one")
@@ -386,14 +405,15 @@ class Run:
         self.plan = plan(args, E, env.episode_limit, T, self.world)
         if self.single:
             self.replay = SingleUbsSequenceReplay(int(args.replay_size), T, env.n_gts, args.hidden_size, n_envs=E, device=dev,
-                                                  device_state=True, seed=seeds["replay"])
+                                                  device_state=True, seed=seeds["replay"], prioritized=self.prioritized)
         elif self.compact_replay:                # simulator state instead of observations: the same update inputs, bit for bit
             self.replay = CompactSequenceReplay.for_env(env, int(args.replay_size), T, args.hidden_size,
-                                                        rew_dim=1 if args.share_reward else None, seed=seeds["replay"])
+                                                        rew_dim=1 if args.share_reward else None, seed=seeds["replay"],
+                                                        prioritized=self.prioritized)
         else:
             self.replay = SequenceReplay(int(args.replay_size), T, env.n_agents, env.n_gts, args.hidden_size, n_envs=E,
                                          r_comm=env.p.r_comm, rew_dim=1 if args.share_reward else None, device=dev,
-                                         device_state=True, seed=seeds["replay"])
+                                         device_state=True, seed=seeds["replay"], prioritized=self.prioritized)
         graphed = bool(ours["graphed"])
         ep_cls, ev_cls = (GraphedEpisode, GraphedEvaluation) if graphed else (Episode, Evaluation)
         kw = dict(eps=(EPS_START, EPS_END, float(args.decay_steps)), updates_per_segment=int(ours["updates_per_segment"]), enc=enc)
@@ -418,7 +438,7 @@ class Run:
     @classmethod
     def create(cls, exp: str, env, args, output_dir: str, exp_name: Optional[str] = None, seed: int = 0, n_envs: int = 32,
                n_test_envs: Optional[int] = None, updates_per_segment: int = 1, graphed: bool = True, save_replay: bool = True,
-               group=None, force_collective: bool = False, compact_replay: bool = False) -> "Run":
+               group=None, force_collective: bool = False, compact_replay: bool = False, prioritized=None) -> "Run":
         """Builds simulators, learner, replay, statistics, film and the three graphs (``graphed=False``: their eager forms) as
         run.py:47-61 builds them and writes ``config.json``; sets torch's generator (``torch.manual_seed(seed)``, as the reference's
         ``set_rand_seed`` does) for the parameter initialisation.  env: a map id of ``sim.MAPS`` or a ``MapSpec`` (exp2 / exp3), a
@@ -427,6 +447,9 @@ class Run:
         interactions again before it trains and is NOT bit-identical to an uninterrupted one.
         compact_replay=True (exp2 / exp3): the ring is a ``replay.CompactSequenceReplay`` - simulator state instead of observations,
         about 18 x fewer bytes per sequence in HBM and in ``state.pt``, the same update inputs bit for bit; exp1: ``ValueError``.
+        prioritized=(alpha, beta, eta, eps): proportional prioritised replay over sequences on the device (``replay._RingState``) - the
+        ring draws by priority, the loss carries the importance weights and every update rewrites the priorities of its batch;
+        ``state.pt`` then holds ``replay.prio`` / ``replay.prio_max``.  None (the default): the uniform sampler, nothing changes.
 
         With ``torch.distributed`` initialised the run is data-parallel over ``group`` (default: the world) and EVERY rank calls
         ``create`` with the same arguments but its own ``args.device``; ``n_envs`` and ``args.batch_size`` are per rank.
@@ -435,7 +458,7 @@ class Run:
         ns = check_args(exp, args)
         world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         ours = run_config(exp, env, ns, seed, n_envs, n_test_envs, updates_per_segment, graphed, save_replay, world, force_collective,
-                          compact_replay)
+                          compact_replay, prioritized)
         run = cls(ours, ns, output_dir, exp_name, resuming=False, group=group)
         if run.rank == 0:
             env_fn, env_kwargs = _reference_env(exp, env)
@@ -507,6 +530,8 @@ class Run:
         for name, ep in (("collect", self.collect), ("train", self.train_episode)):
             out.update({f"{name}.t": ep.t, f"{name}.eps": ep.eps, f"{name}.explore": ep.explore})
         out.update({"comm." + name: m.rng_state for name, m in comm_modules(lr)})
+        if self.prioritized is not None:
+            out.update({"replay.prio": rb.prio, "replay.prio_max": rb.prio_max})
         return out
 
     def _save_state(self) -> None:
@@ -665,6 +690,9 @@ def _parser():
     ap.add_argument("--no-save-replay", action="store_true")
     ap.add_argument("--compact-replay", action="store_true",
                     help="exp2 / exp3: the ring stores simulator state and rebuilds the observations (replay.CompactSequenceReplay)")
+    ap.add_argument("--prioritized", type=float, nargs=4, default=None, metavar=("ALPHA", "BETA", "ETA", "EPS"),
+                    help="proportional prioritised replay over sequences: priority exponent, importance-weight exponent, max/mean mix "
+                         "of |TD| per sequence, and the constant added before the exponent (no defaults: four numbers)")
     ap.add_argument("--epochs", type=int, default=None, help="run this many more epochs, not all remaining ones")
     ap.add_argument("--dist-backend", choices=("nccl", "gloo"), default="nccl", help="under a launcher that sets RANK: the backend of the group")
     ap.add_argument("--dist-timeout", type=float, default=600.0, help="seconds after which a collective gives up on a missing rank")
@@ -688,7 +716,7 @@ def main(argv=None) -> None:
                 args["device"] = device
             run = Run.create(a.exp, _parse_env(a.exp, a.env), args, a.out, exp_name=a.exp_name or a.exp, seed=a.seed, n_envs=a.envs,
                              n_test_envs=a.test_envs, updates_per_segment=a.updates_per_segment, graphed=not a.eager,
-                             save_replay=not a.no_save_replay, compact_replay=a.compact_replay)
+                             save_replay=not a.no_save_replay, compact_replay=a.compact_replay, prioritized=a.prioritized)
         run.train(a.epochs)
         if run.rank == 0:
             print(f"{a.out}: epoch {run.epoch} of {run.plan.epochs}, {run.interacts} interactions, {run.elapsed:.1f} s")
