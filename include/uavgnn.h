@@ -402,6 +402,36 @@ int uavgnn_qmix_mix_fwd(const float* proj, long long ld_proj, const float* qs, c
 int uavgnn_qmix_mix_bwd(const float* proj, long long ld_proj, const float* qs, const float* d_qtot, const float* v2w, int rows, int n,
                         int e, float* d_proj, long long ld_dproj, float* d_qs, float* partials, int G, uavgnn_stream_t stream);
 int uavgnn_qmix_mix_bwd_partials(int rows, int e);
+/* ---- TD tail behind the Q head (csrc/td_return.hip; reference: algos/madrqn/learner.py:134-154) ----------------------------------
+ * Action select, multi-step targets, TD errors, loss and its gradient (DESIGN: "Multi-step TD targets").  All operands are contiguous
+ * fp32 unless said otherwise; plain dword accesses, no atomics, deterministic; arguments only (no environment is read).  T, N, A, B, C
+ * below 1, a NULL required operand or a size that does not match is UAVGNN_EINVAL, and nothing is launched.
+ * _td_select_fwd (learner.py:134-143): agent_out [T+1, N, A], target_out [T, N, A], acts [T, N] int64 ->
+ *   qvals [T, N] = agent_out[t, n, acts[t, n]] (NaN for an index outside [0, A): nothing is read there),
+ *   next_acts [T, N] int32 (may be NULL) = argmax_a agent_out[t+1, n, a] if double_q, else argmax_a target_out[t, n, a],
+ *   next_vals [T, N] = target_out[t, n, next_acts[t, n]].  The first maximum wins and a NaN counts as the maximum (torch.argmax / max).
+ * _td_select_bwd (learner.py:134 under loss.backward(), :157): d_agent_out [T+1, N, A], EVERY element written (so the caller hands in
+ *   uninitialised memory): d_qvals[t, n] (times *scale, a device scalar, when scale is not NULL) at (t, n, acts[t, n]), exact zeros
+ *   elsewhere and in all of row T.
+ * _td_return_fwd (learner.py:145-154, extended): qvals, next_vals [T, B, C]; rews [T, B, Cr], Cr = 1 (broadcast) or C; dones [T, B, 1];
+ *   weights [B] or NULL (= 1); c_t = gamma (1 - done_t).  mode UAVGNN_TD_NSTEP with n_step >= 1 (lam is not read):
+ *     y_t = sum_{k<m} (prod_{j<k} c_{t+j}) r_{t+k} + (prod_{j<m} c_{t+j}) V_{t+m-1},  m = min(n_step, T - t);
+ *   mode UAVGNN_TD_LAMBDA with 0 <= lam <= 1 (n_step is not read):
+ *     G_{T-1} = r_{T-1} + c_{T-1} V_{T-1},  G_t = r_t + c_t ((1 - lam) V_t + lam G_{t+1}),  y_t = G_t.
+ *   Outputs: td [T, B, C] = q - y, g [T, B, C] = (2 w_b / (T B C)) td, loss [1] = sum w_b td^2 / (T B C), summed in two stages in a fixed
+ *   order through workspace [G] floats, G = uavgnn_td_return_partials(B, C) (anything else: UAVGNN_EINVAL).  Every operation of a target
+ *   is rounded once, in the order r + ((gamma (1 - done)) V): n_step = 1 and lam = 0 give learner.py:150's TD errors bit for bit.
+ * _td_return_partials (learner.py:154): G, a function of (B, C) only. */
+#define UAVGNN_TD_NSTEP 0
+#define UAVGNN_TD_LAMBDA 1
+int uavgnn_td_select_fwd(const float* agent_out, const float* target_out, const long long* acts, int T, long long N, int A, int double_q,
+                         float* qvals, float* next_vals, int* next_acts, uavgnn_stream_t stream);
+int uavgnn_td_select_bwd(const float* d_qvals, const long long* acts, const float* scale, int T, long long N, int A, float* d_agent_out,
+                         uavgnn_stream_t stream);
+int uavgnn_td_return_fwd(const float* qvals, const float* next_vals, const float* rews, int Cr, const float* dones, const float* weights,
+                         int T, int B, int C, float gamma, int mode, int n_step, float lam, float* td, float* g, float* loss,
+                         float* workspace, int G, uavgnn_stream_t stream);
+int uavgnn_td_return_partials(int B, int C);
 /* ---- dense layers on the f16 matrix cores, exactly scaled two-term splits (csrc/gemm_h2.hip, round 6) -----------------------------
  * Y = [X (K1 columns) || X2 (K - K1 columns; NULL: one source, K1 = K)] B^T (+ bias) (+ Y) (ReLU): the products of
  * uavgnn_gemm_nt_x3 / _cat with THREE f16 x f16 MFMA products per fp32 product instead of six bf16 ones (arithmetic, error and

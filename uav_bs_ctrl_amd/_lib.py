@@ -116,6 +116,11 @@ SIGNATURES = {
     "uavgnn_qmix_mix_bwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_fp, ctypes.c_longlong, _c_fp,
                                      _c_fp, _c_int, _c_st]),
     "uavgnn_qmix_mix_bwd_partials": (_c_int, [_c_int, _c_int]),
+    "uavgnn_td_select_fwd": (_c_int, [_c_fp, _c_fp, ctypes.c_void_p, _c_int, ctypes.c_longlong, _c_int, _c_int, _c_fp, _c_fp, _c_ip, _c_st]),
+    "uavgnn_td_select_bwd": (_c_int, [_c_fp, ctypes.c_void_p, _c_fp, _c_int, ctypes.c_longlong, _c_int, _c_fp, _c_st]),
+    "uavgnn_td_return_fwd": (_c_int, [_c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f32, _c_int, _c_int, _c_f32,
+                                      _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_st]),
+    "uavgnn_td_return_partials": (_c_int, [_c_int, _c_int]),
     "uavgnn_relu_bwd_colsum": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_int, _c_int, _c_fp,
                                _c_int, _c_st]),
     "uavgnn_relu_bwd_colsum_rowmax": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_int, _c_int,

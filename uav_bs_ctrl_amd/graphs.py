@@ -318,7 +318,10 @@ class _GraphedUpdateBase:
         return self.learner.update(self._batch())
 
     def _bind_weights(self, weights: Optional[th.Tensor], T: int, B: int, C: int) -> None:
-        """``weights`` [B] (None: the update is not prioritised) and the TD buffer ``td`` [T, B, C] the loss writes into."""
+        """``weights`` [B] (None: the update is not prioritised) and the TD buffer ``td`` [T, B, C] the loss writes into.  A learner with
+        multi-step targets (``learner.returns``) needs nothing more of a captured update: its kernel writes ``td`` itself (no copy), the
+        partial sums of its loss live in the learner's own per-shape workspace, allocated by the warm-up before the capture, and the
+        gradient buffer in the capture's pool - fixed addresses all."""
         self.weights, self.td = weights, None
         if weights is None:
             return

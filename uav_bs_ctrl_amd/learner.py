@@ -85,8 +85,14 @@ def broadcast_parameters(module: th.nn.Module, src: int = 0, group=None, force: 
 
 
 class MultiAgentQLearner:
-    def __init__(self, env_info: dict, args, process_group=None):
+    """returns: the TD target of ``update`` - None (the reference's one-step target, learner.py:150; every launch as it was),
+    ``("nstep", n)`` with an integer n >= 1 or ``("lambda", lam)`` with 0 <= lam <= 1: multi-step targets over the stored sequence
+    (``ops.td_return_loss``; DESIGN "Multi-step TD targets")."""
+
+    def __init__(self, env_info: dict, args, process_group=None, returns=None):
         self.args = args
+        self.returns = ops.normalize_returns(returns)
+        self._td_workspace = {}       # ops.td_return_loss: the loss's partial sums, one buffer per shape (fixed addresses under capture)
         self.device = th.device(args.device)
         self.obs_shape = env_info["obs_shape"]
         self.n_actions = env_info["n_actions"]
@@ -294,6 +300,8 @@ class MultiAgentQLearner:
 
     def _td_loss(self, batch: Dict, T: int, agent_out: th.Tensor, target_out: th.Tensor) -> tuple:
         """learner.py:134-154 on the stacked Q values agent_out [T+1, N, n_actions] / target_out [T, N, n_actions]."""
+        if self.returns is not None:
+            return self._td_loss_returns(batch, T, agent_out, target_out)
         qvals = agent_out[:-1].gather(2, batch["acts"])
         if self.double_q:
             next_acts = agent_out[1:].detach().argmax(2, keepdim=True)
@@ -325,6 +333,30 @@ class MultiAgentQLearner:
         else:                                            # inside `accumulate`: one entry per chunk
             chunks.append(td)
         return _weighted_mse(d, weights), agent_out, target_out
+
+    def _td_loss_returns(self, batch: Dict, T: int, agent_out: th.Tensor, target_out: th.Tensor) -> tuple:
+        """``_td_loss`` with ``returns`` set: select -> mixers (unchanged) -> multi-step targets, TD errors and loss
+        (``ops.td_select`` / ``ops.td_return_loss``: csrc/td_return.hip on the GPU).  Same contract for ``weights``, ``td_out``,
+        ``last_td`` and ``_td_chunks``.  The stored ``done`` is the only cut of a sequence (``graphs.Episode`` refuses
+        ``episode_limit % T != 0``, so no sequence of the device loop straddles a reset; a hand-built ring that does is the caller's
+        business)."""
+        qvals, next_vals = ops.td_select(agent_out, target_out, batch["acts"], self.double_q)
+        B = batch["rews"].shape[1]
+        qvals = qvals.view(T, B, self.n_agents)
+        next_vals = next_vals.view(T, B, self.n_agents)
+        if self.mixer is not None:                       # learner.py:145-148 (batch["states"]: [T+1, B, state_dim])
+            qvals = self.mixer(qvals, batch["states"][:-1])
+            next_vals = self.target_mixer(next_vals, batch["states"][1:])
+        weights = batch.get("weights")
+        loss, td = ops.td_return_loss(qvals, next_vals, batch["rews"], batch["dones"], weights, self.gamma, self.returns,
+                                      td_out=batch.get("td_out") if weights is not None else None, workspace=self._td_workspace)
+        if weights is not None:
+            chunks = getattr(self, "_td_chunks", None)
+            if chunks is None:
+                self.last_td = [td]
+            else:
+                chunks.append(td)
+        return loss, agent_out, target_out
 
     def update(self, batch) -> Dict:
         """One gradient step = ``accumulate`` (loss + backward into the flat gradient buffer) -> the ONE collective of the
@@ -459,9 +491,10 @@ class QLearner(MultiAgentQLearner):
 
     env_info: the wrapper's dict (``BatchedSingleUbsCoverageEnv.get_env_info``: obs_shape, n_actions, episode_limit).  args: the
     reference's DRQN config (algos/drqn/config.py); ``dueling`` defaults to False when it is missing (the DRQN config has no
-    such switch), ``double_q`` and ``mixer`` are not read.  The caller's ``args`` object is left as it is."""
+    such switch), ``double_q`` and ``mixer`` are not read.  The caller's ``args`` object is left as it is.  returns: passed through to
+    the parent (multi-step targets on ``max`` bootstrap values, C = 1)."""
 
-    def __init__(self, env_info: dict, args, process_group=None):
+    def __init__(self, env_info: dict, args, process_group=None, returns=None):
         import copy
         args = copy.copy(args)
         if not hasattr(args, "dueling"):
@@ -469,7 +502,7 @@ class QLearner(MultiAgentQLearner):
         args.double_q, args.mixer = False, False
         info = dict(env_info)
         info["n_agents"] = 1
-        super().__init__(info, args, process_group)
+        super().__init__(info, args, process_group, returns)
 
     def _build_agent(self):
         """learner.py:48-52: an integer observation size -> 'rnn' (flattened observations), a dict of feature sizes -> the

@@ -1085,6 +1085,175 @@ def qmix_mix(proj, qs, v2_weight, v2_bias):
     return _QmixMix.apply(proj, qs, v2_weight, v2_bias)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# TD tail behind the Q head (csrc/td_return.hip): action select, multi-step targets, TD errors, loss and its gradient
+# ---------------------------------------------------------------------------------------------------------------------
+def normalize_returns(returns):
+    """``None`` (the reference's one-step target, learner.py:150), ``("nstep", n)`` with an integer n >= 1 or ``("lambda", lam)`` with
+    0 <= lam <= 1 -> None or the pair with n an int / lam a float.  Anything else is a ValueError that names the value."""
+    if returns is None:
+        return None
+    try:
+        kind, value = returns
+    except (TypeError, ValueError):
+        raise ValueError(f"returns: None, ('nstep', n) or ('lambda', lam) expected, got {returns!r}") from None
+    if kind == "nstep":
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not 1 <= value <= 2 ** 30 or value != int(value):
+            raise ValueError(f"returns=('nstep', n): n must be an integer >= 1, got {value!r}")
+        return "nstep", int(value)
+    if kind == "lambda":
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not 0.0 <= float(value) <= 1.0:
+            raise ValueError(f"returns=('lambda', lam): lam must be a number in [0, 1], got {value!r}")
+        return "lambda", float(value)
+    raise ValueError(f"returns: the kind is 'nstep' or 'lambda', got {kind!r} in {returns!r}")
+
+
+def td_targets_torch(next_vals, rews, dones, gamma, returns):
+    """The two multi-step targets in torch ops (what runs on CPU tensors, and the comparison arm of tools/td_return_probe.py).
+    next_vals [T, B, C], rews [T, B, C] or [T, B, 1], dones [T, B, 1] -> y [T, B, C]; with c_t = gamma (1 - done_t):
+      ('nstep', n):    y_t = sum_{k<m} (prod_{j<k} c_{t+j}) r_{t+k} + (prod_{j<m} c_{t+j}) V_{t+m-1}, m = min(n, T - t), as min(n, T) passes
+                       over the whole sequence: y^(1) = r + c V, y^(k)_t = r_t + c_t y^(k-1)_{t+1} (t < T - 1), y^(k)_{T-1} = y^(1)_{T-1};
+      ('lambda', lam): G_{T-1} = r_{T-1} + c_{T-1} V_{T-1}, G_t = r_t + c_t ((1 - lam) V_t + lam G_{t+1}), a loop over T."""
+    kind, p = normalize_returns(returns)
+    T = next_vals.shape[0]
+    rews = rews.expand_as(next_vals)
+    c = (gamma * (1 - dones)).expand_as(next_vals)
+    if kind == "nstep":
+        y = rews + c * next_vals
+        for _ in range(min(p, T) - 1):
+            y = th.cat([rews[:-1] + c[:-1] * y[1:], y[-1:]])
+        return y
+    G = rews[T - 1] + c[T - 1] * next_vals[T - 1]
+    ys = [G]
+    for t in range(T - 2, -1, -1):
+        G = rews[t] + c[t] * ((1 - p) * next_vals[t] + p * G)
+        ys.append(G)
+    return th.stack(ys[::-1])
+
+
+class _TdSelect(th.autograd.Function):
+    """learner.py:134-143 in one pass over the two Q tensors; the backward writes all of d_agent_out (no zeros + scatter)."""
+
+    @staticmethod
+    def forward(ctx, agent_out, target_out, acts, double_q):
+        L.require_gpu(agent_out, target_out, acts)
+        agent_out, target_out = L.f32c(agent_out), L.f32c(target_out)
+        T1, N, A = agent_out.shape
+        T = T1 - 1
+        if tuple(target_out.shape) != (T, N, A) or acts.dtype != th.int64 or acts.numel() != T * N:
+            raise L.UavGnnError(f"td_select: agent_out {tuple(agent_out.shape)}, target_out {tuple(target_out.shape)}, acts "
+                                f"{tuple(acts.shape)} {acts.dtype} do not fit [T+1, N, A] / [T, N, A] / [T, N] int64")
+        acts = acts if acts.is_contiguous() else acts.contiguous()
+        qvals = th.empty((T, N), dtype=th.float32, device=agent_out.device)
+        next_vals, next_acts = th.empty_like(qvals), th.empty((T, N), dtype=th.int32, device=agent_out.device)
+        with KERNEL_TIMER.span("td_select_fwd", (T, N, A)):
+            rc = L.lib().uavgnn_td_select_fwd(agent_out.data_ptr(), target_out.data_ptr(), acts.data_ptr(), T, N, A, int(bool(double_q)),
+                                              qvals.data_ptr(), next_vals.data_ptr(), next_acts.data_ptr(), L.stream())
+        L.check(rc, "uavgnn_td_select_fwd")
+        ctx.save_for_backward(acts)
+        ctx.dims = (T, N, A)
+        ctx.mark_non_differentiable(next_vals, next_acts)
+        return qvals, next_vals, next_acts
+
+    @staticmethod
+    def backward(ctx, d_qvals, _d_next, _d_acts):
+        acts, = ctx.saved_tensors
+        T, N, A = ctx.dims
+        d_qvals = L.f32c(d_qvals)
+        d_agent_out = th.empty((T + 1, N, A), dtype=th.float32, device=d_qvals.device)
+        with KERNEL_TIMER.span("td_select_bwd", (T, N, A)):
+            rc = L.lib().uavgnn_td_select_bwd(d_qvals.data_ptr(), acts.data_ptr(), None, T, N, A, d_agent_out.data_ptr(), L.stream())
+        L.check(rc, "uavgnn_td_select_bwd")
+        return d_agent_out, None, None, None
+
+
+def td_select(agent_out, target_out, acts, double_q, return_acts=False):
+    """agent_out [T+1, N, A], target_out [T, N, A], acts [T, N] or [T, N, 1] int64 -> (qvals [T, N], next_vals [T, N]): Q(s_t, a_t), and
+    the bootstrap value target_out[t] at the double-Q choice argmax_a agent_out[t+1] (``double_q``) or its row maximum.  Only qvals
+    carries a gradient.  return_acts: also the chosen next actions [T, N] (int32 on the GPU).  CUDA tensors run csrc/td_return.hip, CPU
+    tensors the torch chain of ``learner._td_loss``."""
+    if agent_out.is_cuda:
+        qvals, next_vals, next_acts = _TdSelect.apply(agent_out, target_out, acts, double_q)
+    else:
+        T, N = target_out.shape[0], target_out.shape[1]
+        qvals = agent_out[:-1].gather(2, acts.reshape(T, N, 1)).view(T, N)
+        next_acts = (agent_out[1:] if double_q else target_out).detach().argmax(2, keepdim=True)
+        next_vals = target_out.detach().gather(2, next_acts).view(T, N)
+        next_acts = next_acts.view(T, N)
+    return (qvals, next_vals, next_acts) if return_acts else (qvals, next_vals)
+
+
+class _TdReturnLoss(th.autograd.Function):
+    """Targets, TD errors, loss and g = d loss / d qvals in one call (csrc/td_return.hip); the backward is g * grad_output."""
+
+    @staticmethod
+    def forward(ctx, qvals, next_vals, rews, dones, weights, gamma, returns, td, workspace):
+        L.require_gpu(qvals, next_vals, rews, dones, weights, td)
+        qvals, next_vals, rews, dones = L.f32c(qvals), L.f32c(next_vals), L.f32c(rews), L.f32c(dones)
+        T, B, C = qvals.shape
+        Cr = rews.shape[-1]
+        if tuple(next_vals.shape) != (T, B, C) or tuple(rews.shape) != (T, B, Cr) or dones.numel() != T * B:
+            raise L.UavGnnError(f"td_return_loss: qvals {tuple(qvals.shape)}, next_vals {tuple(next_vals.shape)}, rews {tuple(rews.shape)}, "
+                                f"dones {tuple(dones.shape)} do not fit [T, B, C] / [T, B, C] / [T, B, 1 or C] / [T, B, 1]")
+        if weights is not None:
+            weights = L.f32c(weights)
+            if weights.numel() != B:
+                raise L.UavGnnError(f"td_return_loss: {weights.numel()} weights for {B} sequences")
+        dev = qvals.device
+        if tuple(td.shape) != (T, B, C) or td.dtype != th.float32 or not td.is_contiguous():
+            raise L.UavGnnError(f"td_return_loss: td_out must be a contiguous float32 [{T}, {B}, {C}], got {tuple(td.shape)} {td.dtype}")
+        lib = L.lib()
+        G = lib.uavgnn_td_return_partials(B, C)
+        if G < 1:
+            L.check(G, "uavgnn_td_return_partials")
+        if workspace is None:
+            partials = th.empty(G, dtype=th.float32, device=dev)
+        else:       # the caller's store (the learner's): one buffer per shape, handed to every call
+            partials = workspace.get((G, dev))
+            if partials is None:
+                partials = workspace[(G, dev)] = th.empty(G, dtype=th.float32, device=dev)
+        g = th.empty((T, B, C), dtype=th.float32, device=dev)
+        loss = th.empty((), dtype=th.float32, device=dev)
+        kind, p = returns
+        mode, n_step, lam = (0, p, 0.0) if kind == "nstep" else (1, 0, p)
+        with KERNEL_TIMER.span("td_return_fwd", (T, B, C)):
+            rc = lib.uavgnn_td_return_fwd(qvals.data_ptr(), next_vals.data_ptr(), rews.data_ptr(), Cr, dones.data_ptr(), L.ptr(weights), T, B,
+                                          C, float(gamma), mode, n_step, lam, td.data_ptr(), g.data_ptr(), loss.data_ptr(),
+                                          partials.data_ptr(), G, L.stream())
+        L.check(rc, "uavgnn_td_return_fwd")
+        ctx.save_for_backward(g)
+        return loss
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        g, = ctx.saved_tensors
+        return g * d_loss, None, None, None, None, None, None, None, None
+
+
+def td_return_loss(qvals, next_vals, rews, dones, weights, gamma, returns, td_out=None, workspace=None):
+    """(loss, td) of the multi-step TD target ``returns`` = ('nstep', n) / ('lambda', lam) (definitions: ``td_targets_torch``, DESIGN):
+    qvals, next_vals [T, B, C]; rews [T, B, C] or [T, B, 1]; dones [T, B, 1]; weights [B] or None (= 1).  td [T, B, C] = qvals - y (no
+    gradient; written straight into ``td_out`` when one is given - the fixed-address buffer of a captured update), loss =
+    sum_b w_b td^2 / (T B C) with gradient (2 w_b / (T B C)) td towards qvals only: the targets carry none.  ('nstep', 1) and
+    ('lambda', 0) give the TD errors of the one-step target bit for bit on finite inputs.  workspace: a dict that keeps the per-workgroup
+    partial sums of the loss between calls (None: a fresh buffer per call).  The only cut of a sequence is its stored ``done``; a
+    hand-built ring whose sequences straddle an environment reset without one is the caller's business.  CUDA tensors run
+    csrc/td_return.hip; CPU tensors run ``td_targets_torch``."""
+    returns = normalize_returns(returns)
+    if returns is None:
+        raise ValueError("td_return_loss: returns is ('nstep', n) or ('lambda', lam); the one-step default is learner._td_loss's own chain")
+    if qvals.is_cuda:
+        # td is a plain buffer the kernel fills (the caller's fixed-address one, or a fresh one): it never enters the autograd graph
+        td = td_out if td_out is not None else th.empty(tuple(qvals.shape), dtype=th.float32, device=qvals.device)
+        return _TdReturnLoss.apply(qvals, next_vals, rews, dones, weights, gamma, returns, td, workspace), td
+    d = qvals - td_targets_torch(next_vals.detach(), rews, dones, gamma, returns)
+    x = d.square() if weights is None else d.square() * weights.view(1, -1, 1)
+    td = d.detach()
+    if td_out is not None:
+        td = td_out.copy_(td)
+    return x.sum() / max(d.numel(), 1), td
+
+
 RELU_BWD_FUSED = os.environ.get("UAVGNN_RELU_BWD_FUSED", "1") != "0"   # ReLU mask + bias gradient in one pass (A/B switch)
 
 
