@@ -1396,7 +1396,8 @@ def test_fused_hetero_k1_raw_rows_vs_oracle(monkeypatch):
 
 def test_fused_adamw_clip_polyak_kernel_matches_torch_and_checkpoints_interchange():
     """uavgnn_adamw_polyak over flat buffers == clip_grad_value_ + torch.optim.AdamW.step + the polyak loop of
-    learner.py:157-166, over several steps with a changing learning rate (LambdaLR), odd sizes (tail path, padding) and a
+    learner.py:157-166, over several steps with a changing learning rate (LambdaLR), odd parameter sizes (each padded to four floats
+    by FlatParams, so the kernel's scalar tail is NOT reached from here: tests/test_grid_caps_gpu.py runs it through the C ABI) and a
     clip boundary inside the buffer; FusedAdamW's state_dict loads into torch.optim.AdamW and vice versa."""
     import torch.nn as nn
     from uav_bs_ctrl_amd.learner import FlatGradBuffer
