@@ -8,7 +8,7 @@ import torch as th
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from uav_bs_ctrl_amd import enable_tuned_gemms, ops  # noqa: E402
+from uav_bs_ctrl_amd import _lib as L, enable_tuned_gemms, ops  # noqa: E402
 
 print("recorded vendor-GEMM solutions:", enable_tuned_gemms())
 dev = th.device("cuda")
@@ -39,7 +39,7 @@ cases = [("f_aggr forward (rollout)      x[N,512] W[256,512]^T", N, 256, 512, Fa
 _a = th.randn(N, 768, device=dev)
 _W = th.randn(768, 256, device=dev) * 0.06
 _y = th.randn(N, 256, device=dev)
-for flags, what in ((8, "4-wave"), (0, "8-wave")):
+for flags, what in ((L.UAVGNN_GEMM_TILE_128, "4-wave"), (0, "8-wave")):
     ops.GEMM_X3_FLAGS = flags
     print(f"GRU dh += d_gh W_hh WITH the accumulate epilogue ({what}): {time_us(lambda: ops.gemm_x3(_a, _W, True, out=_y, accumulate=True)):7.1f} us"
           f" | without: {time_us(lambda: ops.gemm_x3(_a, _W, True, out=_y)):7.1f} us")
@@ -49,10 +49,9 @@ for name, M, n_out, K, tr in cases:
     W = (th.randn(K, n_out, device=dev) if tr else th.randn(n_out, K, device=dev)) * 0.06
     f_x3 = lambda: ops.gemm_x3(a, W, tr)
     f_v = (lambda: th.mm(a, W)) if tr else (lambda: th.mm(a, W.t()))
-    from uav_bs_ctrl_amd import _lib as L
-    ops.GEMM_X3_FLAGS = 8   # UAVGNN_GEMM_TILE_128
+    ops.GEMM_X3_FLAGS = L.UAVGNN_GEMM_TILE_128
     t_x3_w4 = time_us(f_x3)
-    ops.GEMM_X3_FLAGS = 4     # eight waves, staging interleaved with the MFMAs
+    ops.GEMM_X3_FLAGS = L.UAVGNN_GEMM_STAGING_INTERLEAVED     # eight waves, staging interleaved with the MFMAs
     t_x3_il = time_us(f_x3)
     y_il = f_x3()
     ops.GEMM_X3_FLAGS = 0     # the default: eight waves, the staging of a slice as a block in front of its MFMAs

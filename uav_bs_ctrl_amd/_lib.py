@@ -1,5 +1,7 @@
 """ctypes binding of ``libuavgnn.so`` - the C-ABI declared in ``include/uavgnn.h``.
 
+The header is the only place where an entry point or an ABI constant is declared: ``SIGNATURES`` and the ``UAVGNN_*`` constants of
+this module are read from its text at import (``parse_header``); nothing here restates a prototype.
 PyTorch only supplies device memory and the current HIP stream; every call passes raw pointers and sizes.
 There is NO CPU fallback: if the shared library is missing, or a tensor is not on the GPU, the call raises.
 """
@@ -7,212 +9,76 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 
 import torch as th  # imported first on purpose: libuavgnn must bind to the HIP runtime torch already loaded
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UAVGNN_LIB: another build of the same library (kernel A/Bs of the probes: a variant compiled with different -D switches)
 LIB_PATH = os.environ.get("UAVGNN_LIB") or os.path.join(_HERE, "csrc", "libuavgnn.so")
-
-_c_fp = ctypes.c_void_p   # const float* / float*
-_c_ip = ctypes.c_void_p   # const int32_t*
-_c_int = ctypes.c_int
-_c_f32 = ctypes.c_float
-_c_st = ctypes.c_void_p   # hipStream_t
-
-# name -> (restype, argtypes); mirrors include/uavgnn.h one to one (checked by tests/test_cabi_symbols.py)
-SIGNATURES = {
-    "uavgnn_version": (_c_int, []),
-    "uavgnn_strerror": (ctypes.c_char_p, [_c_int]),
-    "uavgnn_gatv2_fwd": (_c_int, [_c_fp, _c_int, _c_int, _c_fp, _c_int, _c_ip, _c_ip, _c_int, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp,
-                                  _c_fp, _c_fp, _c_int, _c_int, _c_f32, _c_fp, _c_int, _c_fp, _c_st]),
-    "uavgnn_gatv2_fwd_valu": (_c_int, [_c_fp, _c_int, _c_int, _c_fp, _c_int, _c_ip, _c_ip, _c_int, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp,
-                                       _c_fp, _c_fp, _c_int, _c_int, _c_f32, _c_fp, _c_int, _c_fp, _c_st]),
-    "uavgnn_gatv2_fwd_mfma": (_c_int, [_c_fp, _c_int, _c_int, _c_fp, _c_int, _c_ip, _c_ip, _c_int, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp,
-                                       _c_fp, _c_fp, _c_int, _c_int, _c_f32, _c_fp, _c_int, _c_fp, _c_st]),
-    "uavgnn_gatv2_hetero_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int]),
-    "uavgnn_gatv2_hetero_fwd": (_c_int, [_c_fp, _c_int, _c_ip, _c_ip, _c_fp, _c_int, _c_ip, _c_fp, _c_int,
-                                         ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), _c_int, _c_int,
-                                         _c_f32, _c_fp, _c_int, _c_fp, _c_fp, _c_st]),
-    "uavgnn_gatv2_hetero_fwd_phases": (_c_int, [_c_fp, _c_int, _c_ip, _c_ip, _c_fp, _c_int, _c_ip, _c_fp, _c_int,
-                                                ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), _c_int,
-                                                _c_int, _c_f32, _c_fp, _c_int, _c_fp, _c_fp, _c_int, _c_st]),
-    "uavgnn_gatv2_hetero_image_bytes": (ctypes.c_size_t, []),
-    "uavgnn_gatv2_hetero_prepare": (_c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), _c_int, _c_int,
-                                             _c_f32, _c_fp, _c_st]),
-    "uavgnn_gatv2_hetero_fwd_image": (_c_int, [_c_fp, _c_int, _c_ip, _c_ip, _c_fp, _c_int, _c_ip, _c_fp, _c_int,
-                                               ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), _c_int,
-                                               _c_int, _c_f32, _c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_int, _c_st]),
-    "uavgnn_gatv2_hetero_fwd_rowmax": (_c_int, [_c_fp, _c_int, _c_ip, _c_ip, _c_fp, _c_int, _c_ip, _c_fp, _c_int,
-                                                ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), _c_int,
-                                                _c_int, _c_f32, _c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_st]),
-    "uavgnn_gatv2_bwd_workspace_bytes": (ctypes.c_size_t, [_c_int, _c_int]),
-    "uavgnn_gatv2_bwd": (_c_int, [_c_fp, _c_int, _c_int, _c_fp, _c_int, _c_ip, _c_ip, _c_int, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp,
-                                  _c_int, _c_int, _c_f32, _c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp,
-                                  _c_fp, _c_fp, _c_fp, ctypes.c_void_p, ctypes.c_size_t, _c_st]),
-    "uavgnn_gatv2_bwd_generic": (_c_int, [_c_fp, _c_int, _c_int, _c_fp, _c_int, _c_ip, _c_ip, _c_int, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp,
-                                  _c_int, _c_int, _c_f32, _c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp,
-                                  _c_fp, _c_fp, _c_fp, ctypes.c_void_p, ctypes.c_size_t, _c_st]),
-    "uavgnn_talk_attn_fwd": (_c_int, [_c_fp, _c_int, _c_fp, _c_int, _c_fp, _c_int, _c_int, _c_int, _c_ip, _c_ip,
-                                      _c_int, _c_f32, _c_fp, _c_int, _c_fp, _c_fp, _c_int, _c_int, _c_st]),
-    "uavgnn_talk_attn_bwd": (_c_int, [_c_fp, _c_int, _c_fp, _c_int, _c_fp, _c_int, _c_int, _c_int, _c_ip, _c_ip,
-                                      _c_ip, _c_ip, _c_ip, _c_int, _c_f32, _c_fp, _c_fp, _c_int, _c_fp, _c_int,
-                                      _c_fp, _c_int, _c_fp, _c_int, _c_fp, _c_st]),
-    "uavgnn_disc_comm_fwd": (_c_int, [_c_fp, _c_int, _c_fp, _c_fp, _c_int, _c_ip, _c_ip, _c_int, _c_f32, _c_fp, _c_int, _c_fp,
-                                      _c_ip, _c_st]),
-    "uavgnn_gumbel_noise": (_c_int, [_c_fp, ctypes.c_longlong, _c_int, _c_fp, _c_st]),
-    "uavgnn_disc_comm_bwd": (_c_int, [_c_fp, _c_int, _c_fp, _c_ip, _c_int, _c_ip, _c_ip, _c_ip, _c_int, _c_f32, _c_fp,
-                                      _c_int, _c_st]),
-    "uavgnn_obs_degrees": (_c_int, [_c_fp, _c_int, _c_int, _c_fp, _c_int, _c_int, _c_int, _c_ip, _c_ip, _c_st]),
-    "uavgnn_obs_compact": (_c_int, [_c_fp, _c_int, _c_int, _c_fp, _c_int, _c_int, _c_int, _c_ip, _c_ip, _c_fp, _c_fp,
-                                    _c_st]),
-    "uavgnn_talk_degrees": (_c_int, [_c_fp, _c_int, _c_int, _c_f32, _c_ip, _c_ip, _c_st]),
-    "uavgnn_offsets_scan4": (_c_int, [_c_ip, _c_int, _c_ip, _c_ip, _c_int, _c_ip, _c_ip, _c_int, _c_ip, _c_ip, _c_int, _c_ip, _c_st]),
-    "uavgnn_talk_compact": (_c_int, [_c_fp, _c_int, _c_int, _c_f32, _c_ip, _c_ip, _c_ip, _c_ip, _c_st]),
-    "uavgnn_build_graph_small_max_agents": (_c_int, []),
-    "uavgnn_build_graph_small": (_c_int, [_c_fp, _c_int, _c_int, _c_fp, _c_int, _c_int, _c_fp, _c_int, _c_int, _c_f32, _c_ip, _c_ip,
-                                          _c_ip, _c_fp, _c_fp, _c_ip, _c_ip, _c_ip, _c_st]),
-    "uavgnn_degree_order_workspace_bytes": (ctypes.c_size_t, [_c_int]),
-    "uavgnn_degree_order": (_c_int, [_c_ip, _c_int, _c_ip, ctypes.c_void_p, ctypes.c_size_t, _c_st]),
-    "uavgnn_csc_transpose_workspace_bytes": (ctypes.c_size_t, [_c_int]),
-    "uavgnn_csc_transpose": (_c_int, [_c_ip, _c_ip, _c_int, _c_int, _c_ip, _c_ip, _c_ip, ctypes.c_void_p,
-                                      ctypes.c_size_t, _c_st]),
-    "uavgnn_csc_transpose_env": (_c_int, [_c_ip, _c_ip, _c_ip, _c_int, _c_int, _c_ip, _c_ip, _c_ip, _c_st]),
-    "uavgnn_talk_attn_env_supported": (_c_int, [_c_int, _c_int, _c_int]),
-    "uavgnn_tarmac_msg_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int]),
-    "uavgnn_tarmac_msg_weight_bytes": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
-    "uavgnn_tarmac_msg_prepare": (_c_int, [_c_fp, _c_int, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_st]),
-    "uavgnn_tarmac_msg_fwd": (_c_int, [_c_fp, _c_int, _c_fp, _c_int, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_fp, _c_int, _c_int,
-                                       _c_ip, _c_ip, _c_f32, _c_fp, _c_int, _c_fp, _c_fp, _c_int, _c_fp, _c_int, _c_st]),
-    "uavgnn_talk_attn_env_fwd": (_c_int, [_c_fp, _c_int, _c_fp, _c_int, _c_fp, _c_int, _c_int, _c_int, _c_ip, _c_ip,
-                                          _c_ip, _c_int, _c_int, _c_f32, _c_fp, _c_int, _c_fp, _c_fp, _c_int, _c_int,
-                                          _c_st]),
-    "uavgnn_talk_attn_env_bwd": (_c_int, [_c_fp, _c_int, _c_fp, _c_int, _c_fp, _c_int, _c_int, _c_int, _c_ip, _c_ip,
-                                          _c_ip, _c_int, _c_int, _c_f32, _c_fp, _c_fp, _c_int, _c_fp, _c_int, _c_fp,
-                                          _c_int, _c_fp, _c_int, _c_st]),
-    "uavgnn_eps_greedy": (_c_int, [_c_fp, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp, _c_f32, ctypes.c_void_p, _c_st]),
-    "uavgnn_eps_greedy_dev": (_c_int, [_c_fp, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp, _c_fp, ctypes.c_void_p, _c_st]),
-    "uavgnn_eps_schedule": (_c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_fp, _c_st]),
-    "uavgnn_eps_greedy_philox": (_c_int, [_c_fp, _c_int, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_fp, _c_f32, ctypes.c_void_p, _c_st]),
-    "uavgnn_stats_push": (_c_int, [ctypes.c_void_p, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_st]),
-    "uavgnn_film_click_mubs": (_c_int, [_c_int] * 6 + [_c_fp] * 10 + [_c_st]),
-    "uavgnn_film_click_subs": (_c_int, [_c_int] * 4 + [ctypes.c_double, _c_int, _c_int] + [_c_fp] * 17 + [_c_st]),
-    "uavgnn_replay_commit": (_c_int, [ctypes.POINTER(ctypes.c_longlong), _c_int, _c_int, _c_int, ctypes.c_void_p, _c_st]),
-    "uavgnn_replay_sample": (_c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_int, _c_int, ctypes.c_void_p, _c_ip, _c_st]),
-    "uavgnn_replay_sample_wide_workspace_bytes": (ctypes.c_longlong, [_c_int]),
-    "uavgnn_replay_sample_wide_slots_per_workgroup": (_c_int, []),
-    "uavgnn_replay_sample_wide": (_c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_int, _c_int, ctypes.c_void_p, _c_ip, ctypes.c_void_p, _c_st]),
-    "uavgnn_replay_gather": (_c_int, [ctypes.POINTER(ctypes.c_longlong), _c_int, ctypes.c_void_p, _c_int, _c_st]),
-    "uavgnn_replay_prio_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int]),
-    "uavgnn_replay_prio_commit": (_c_int, [ctypes.c_void_p, _c_int, _c_int, ctypes.c_void_p, ctypes.c_void_p, _c_st]),
-    "uavgnn_replay_prio_sample": (_c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_int, _c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
-                                           _c_fp, _c_ip, ctypes.c_void_p, _c_st]),
-    "uavgnn_replay_prio_update": (_c_int, [_c_fp, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_int, ctypes.c_double, ctypes.c_double,
-                                           ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, _c_ip, _c_st]),
-    "uavgnn_replay_rebuild_obs": (_c_int, [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double), _c_fp, _c_fp, _c_fp, _c_fp, _c_int,
-                                           _c_int, ctypes.c_void_p, _c_int, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_fp, _c_st]),
-    "uavgnn_colsum_acc": (_c_int, [_c_fp, ctypes.c_longlong, _c_int, _c_int, _c_fp, _c_int, _c_st]),
-    "uavgnn_qmix_mix_fwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_fp, _c_st]),
-    "uavgnn_qmix_mix_bwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_fp, ctypes.c_longlong, _c_fp,
-                                     _c_fp, _c_int, _c_st]),
-    "uavgnn_qmix_mix_bwd_partials": (_c_int, [_c_int, _c_int]),
-    "uavgnn_td_select_fwd": (_c_int, [_c_fp, _c_fp, ctypes.c_void_p, _c_int, ctypes.c_longlong, _c_int, _c_int, _c_fp, _c_fp, _c_ip, _c_st]),
-    "uavgnn_td_select_bwd": (_c_int, [_c_fp, ctypes.c_void_p, _c_fp, _c_int, ctypes.c_longlong, _c_int, _c_fp, _c_st]),
-    "uavgnn_td_return_fwd": (_c_int, [_c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f32, _c_int, _c_int, _c_f32,
-                                      _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_st]),
-    "uavgnn_td_return_partials": (_c_int, [_c_int, _c_int]),
-    "uavgnn_relu_bwd_colsum": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_int, _c_int, _c_fp,
-                               _c_int, _c_st]),
-    "uavgnn_relu_bwd_colsum_rowmax": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_int, _c_int,
-                                               _c_fp, _c_int, _c_fp, _c_st]),
-    "uavgnn_flat_obs_supported": (_c_int, [_c_int, _c_int]),
-    "uavgnn_flat_obs_fwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_int, _c_fp, ctypes.c_longlong, _c_int, _c_fp, ctypes.c_longlong, _c_int,
-                                     _c_int, _c_fp, _c_fp, _c_int, _c_fp, ctypes.c_longlong, _c_st]),
-    "uavgnn_flat_obs_wgrad_chunks": (_c_int, [ctypes.c_longlong, _c_int, _c_int]),
-    "uavgnn_flat_obs_wgrad": (_c_int, [_c_fp, ctypes.c_longlong, _c_int, _c_fp, ctypes.c_longlong, _c_int, _c_fp, ctypes.c_longlong, _c_int,
-                                       _c_fp, ctypes.c_longlong, _c_int, _c_int, _c_fp, _c_int, _c_int, _c_st]),
-    "uavgnn_gemm_nt_x3_rowmax": (_c_int, [_c_fp, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_int, _c_fp, _c_fp, _c_int, _c_int, _c_fp, _c_st]),
-    "uavgnn_col_absmax": (_c_int, [_c_fp, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_fp, _c_st]),
-    "uavgnn_gemm_tn_h2_supported": (_c_int, [ctypes.c_longlong, _c_int, _c_int]),
-    "uavgnn_gemm_tn_h2_chunks": (_c_int, [ctypes.c_longlong, _c_int, _c_int]),
-    "uavgnn_gemm_tn_h2": (_c_int, [_c_fp, ctypes.c_longlong, _c_int, _c_fp, ctypes.c_longlong, _c_int, ctypes.c_longlong, _c_fp, _c_fp, _c_fp,
-                                   _c_int, _c_int, _c_st]),
-    "uavgnn_gemm_tn_h2_width": (_c_int, [_c_int]),
-    "uavgnn_gemm_tn_h2_chunks_tj": (_c_int, [ctypes.c_longlong, _c_int, _c_int, _c_int]),
-    "uavgnn_gemm_tn_h2_tj": (_c_int, [_c_fp, ctypes.c_longlong, _c_int, _c_fp, ctypes.c_longlong, _c_int, ctypes.c_longlong, _c_fp, _c_fp, _c_fp,
-                                      _c_int, _c_int, _c_int, _c_st]),
-    "uavgnn_gemm_h2_supported": (_c_int, [_c_int, _c_int, _c_int]),
-    "uavgnn_split_h2_bytes": (ctypes.c_longlong, [_c_int, _c_int]),
-    "uavgnn_split_h2": (_c_int, [_c_fp, _c_int, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_st]),
-    "uavgnn_gemm_nt_h2": (_c_int, [_c_fp, _c_int, _c_int, _c_fp, _c_int, _c_int, _c_int, _c_fp, _c_fp, ctypes.c_void_p, _c_int, _c_fp, _c_fp,
-                                   _c_int, _c_int, _c_st]),
-    "uavgnn_gemm_nt_h2_rm2": (_c_int, [_c_fp, _c_int, _c_int, _c_fp, _c_int, _c_int, _c_int, _c_fp, _c_fp, ctypes.c_void_p, _c_int, _c_fp, _c_fp,
-                                       _c_int, _c_int, _c_st]),
-    "uavgnn_gemm_nt_h2_n64": (_c_int, [_c_fp, _c_int, _c_int, _c_int, _c_fp, ctypes.c_void_p, _c_int, _c_fp, _c_int, _c_st]),
-    "uavgnn_env_state_dim": (_c_int, [_c_int, _c_int, _c_int]),
-    "uavgnn_env_step": (_c_int, [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double), _c_int] + [_c_fp] * 22 + [_c_st]),
-    "uavgnn_map_sample": (_c_int, [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double), _c_int] + [_c_fp] * 6 + [_c_st]),
-    "uavgnn_subs_env_step": (_c_int, [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double), _c_int] + [_c_fp] * 16 + [_c_st]),
-    "uavgnn_subs_env_sample": (_c_int, [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double), _c_int] + [_c_fp] * 4 + [_c_st]),
-    "uavgnn_adamw_polyak": (_c_int, [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, ctypes.c_longlong, ctypes.c_longlong, _c_fp, ctypes.c_double,
-                                     ctypes.c_double, _c_f32, _c_f32, _c_f32, _c_f32, _c_st]),
-    "uavgnn_gru_cell_supported": (_c_int, [_c_int, _c_int]),
-    "uavgnn_gru_cell_fwd": (_c_int, [_c_fp, _c_int, _c_int, _c_fp, _c_int, _c_int, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_st]),
-    "uavgnn_gru_cell_x3_supported": (_c_int, [_c_int, _c_int]),
-    "uavgnn_gru_cell_x3_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int]),
-    "uavgnn_gru_split_weights": (_c_int, [_c_fp, _c_int, _c_fp, _c_int, ctypes.c_void_p, _c_st]),
-    "uavgnn_gru_cell_fwd_x3": (_c_int, [_c_fp, _c_int, _c_int, _c_fp, _c_int, _c_int, ctypes.c_void_p, _c_fp, _c_fp, _c_fp, _c_fp, _c_st]),
-    "uavgnn_gru_cell_fwd_x3_cat": (_c_int, [_c_fp, _c_int, _c_int, _c_fp, _c_int, _c_int, _c_fp, _c_int, _c_int, ctypes.c_void_p, _c_fp, _c_fp,
-                                            _c_fp, _c_fp, _c_st]),
-    "uavgnn_gru_cell_fwd_x3_opts": (_c_int, [_c_fp, _c_int, _c_int, _c_fp, _c_int, _c_int, _c_fp, _c_int, _c_int, ctypes.c_void_p, _c_fp, _c_fp,
-                                             _c_fp, _c_fp, _c_int, _c_st]),
-    "uavgnn_gru_cell_h2_supported": (_c_int, [_c_int, _c_int]),
-    "uavgnn_gru_cell_h2_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int]),
-    "uavgnn_gru_split_weights_h2": (_c_int, [_c_fp, _c_int, _c_fp, _c_int, ctypes.c_void_p, _c_st]),
-    "uavgnn_gru_cell_fwd_h2": (_c_int, [_c_fp, _c_int, _c_int, _c_fp, _c_int, _c_int, _c_fp, _c_int, _c_int, _c_fp, ctypes.c_void_p, _c_fp,
-                                        _c_fp, _c_fp, _c_fp, _c_st]),
-    "uavgnn_row_absmax": (_c_int, [_c_fp, _c_int, _c_int, _c_fp, _c_int, _c_int, _c_fp, _c_int, _c_int, _c_int, _c_fp, _c_st]),
-    "uavgnn_tarmac_msg_rowmax_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int]),
-    "uavgnn_tarmac_msg_fwd_rowmax": (_c_int, [_c_fp, _c_int, _c_fp, _c_int, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_fp, _c_int, _c_int,
-                                              _c_ip, _c_ip, _c_f32, _c_fp, _c_int, _c_fp, _c_fp, _c_int, _c_fp, _c_int, _c_fp, _c_st]),
-    "uavgnn_gru_cell_bwd_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int]),
-    "uavgnn_gru_split_weights_bwd": (_c_int, [_c_fp, _c_int, _c_fp, _c_int, ctypes.c_void_p, _c_st]),
-    "uavgnn_gru_cell_bwd": (_c_int, [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_fp, _c_fp, _c_fp, _c_int, _c_fp,
-                                     _c_st]),
-    "uavgnn_workspace_bytes": (ctypes.c_longlong, [_c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong]),
-    "uavgnn_gemm_tn_x3_chunks": (_c_int, [ctypes.c_longlong, _c_int, _c_int]),
-    "uavgnn_gemm_tn_x3": (_c_int, [_c_fp, _c_int, _c_int, _c_fp, _c_int, _c_int, ctypes.c_longlong, _c_fp, _c_int, _c_int, _c_st]),
-    "uavgnn_gemm_x3_supported": (_c_int, [_c_int, _c_int, _c_int]),
-    "uavgnn_head_supported": (_c_int, [_c_int, _c_int]),
-    "uavgnn_head_fwd": (_c_int, [_c_fp, _c_int, _c_int, _c_int, _c_fp, _c_int, _c_fp, _c_int, _c_fp, _c_int, _c_st]),
-    "uavgnn_head_duel_supported": (_c_int, [_c_int, _c_int]),
-    "uavgnn_head_fwd_duel": (_c_int, [_c_fp, _c_int, _c_int, _c_int, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_int, _c_st]),
-    "uavgnn_gru_rec_supported": (_c_int, [_c_int]),
-    "uavgnn_gru_rec_fwd": (_c_int, [_c_fp, _c_int, _c_fp, _c_int, _c_int, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_st]),
-    "uavgnn_gru_rec_bwd": (_c_int, [_c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_int, _c_int, _c_fp, _c_fp, _c_fp, _c_fp, _c_st]),
-    "uavgnn_split_bf16x3": (_c_int, [_c_fp, _c_int, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_st]),
-    "uavgnn_gemm_nt_x3": (_c_int, [_c_fp, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_int, _c_fp, _c_fp, _c_int, _c_int, _c_st]),
-    "uavgnn_gemm_nt_x3_cat": (_c_int, [_c_fp, _c_int, _c_int, _c_fp, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_int, _c_fp, _c_fp, _c_int,
-                              _c_int, _c_st]),
-    "uavgnn_gru_gates_bwd_fused": (_c_int, [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_fp, _c_fp, _c_fp, _c_st]),
-    "uavgnn_gru_gates_bwd_fused_head": (_c_int, [_c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_int, _c_int, _c_fp, _c_fp, _c_fp,
-                                                 _c_st]),
-    "uavgnn_gru_gates_bwd_sum_rows": (_c_int, [_c_int, _c_int]),
-    "uavgnn_gru_gates_bwd_fused_sums": (_c_int, [_c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_int, _c_int, _c_fp, _c_fp, _c_fp, _c_fp,
-                                                 _c_st]),
-    "uavgnn_gru_gates_bwd_fused_sums_rowmax": (_c_int, [_c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_int, _c_int, _c_fp, _c_fp, _c_fp, _c_fp,
-                                                        _c_fp, _c_st]),
-    "uavgnn_gru_gates_fwd": (_c_int, [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_fp, _c_st]),
-    "uavgnn_gru_gates_bwd": (_c_int, [_c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_fp, _c_fp, _c_fp, _c_st]),
-}
-
-_LIB = None
-UAVGNN_EINVAL = -1000
-UAVGNN_EUNSUPPORTED = -1001
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "uavgnn.h")   # the include directory build.py compiles against
 
 
 class UavGnnError(RuntimeError):
     pass
+
+
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong,
+            "size_t": ctypes.c_size_t, "uavgnn_stream_t": ctypes.c_void_p}
+# HOST arrays keep a typed pointer (ctypes then refuses an array of another element type); they are told by their parameter name,
+# which no device pointer bears.  Every other pointer is c_void_p: callers pass data_ptr() integers and None.
+_HOST_ARRAYS = {"int_consts": ctypes.POINTER(ctypes.c_int32), "f64_consts": ctypes.POINTER(ctypes.c_double),
+                "fields": ctypes.POINTER(ctypes.c_longlong),
+                "seen_params": ctypes.POINTER(ctypes.c_void_p), "near_params": ctypes.POINTER(ctypes.c_void_p)}
+
+
+def _ctype(words, name, decl):
+    """ctypes class of a result (name None) or of the parameter `name` whose type is the token list `words`."""
+    if "*" in words:
+        if name is None:
+            return ctypes.c_char_p if words == ["const", "char", "*"] else ctypes.c_void_p
+        return _HOST_ARRAYS.get(name, ctypes.c_void_p)
+    c_type = " ".join(w for w in words if w != "const")
+    if c_type not in _SCALARS:      # never a default: ctypes' own (int) is the silent truncation this table exists to rule out
+        raise UavGnnError(f"no ctypes class for the type `{' '.join(words)}` of {name or 'the result'} in the declaration `{decl}`")
+    return _SCALARS[c_type]
+
+
+def parse_header(text: str):
+    """(signatures, constants) of the text of a C header: name -> (restype, [argtypes]) for every ``<type> uavgnn_name(<params>);``
+    and NAME -> value for every ``#define UAVGNN_NAME <integer>``.  Anything it cannot read raises UavGnnError with the declaration."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    constants = {m[1]: int(m[2]) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(UAVGNN_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, re.M)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)                 # preprocessor lines
+    text = re.sub(r'extern\s*"C"\s*\{|\}', "", text)                     # the extern "C" wrapper
+    signatures = {}
+    for decl in text.split(";"):
+        decl = " ".join(decl.split())
+        if not decl or decl.startswith("typedef "):                      # uavgnn_stream_t is in _SCALARS
+            continue
+        m = re.fullmatch(r"(.+?)\b(uavgnn_\w+) ?\((.*)\)", decl)
+        if not m or m[2] in signatures:
+            raise UavGnnError(f"not a prototype `<type> uavgnn_name(<params>)`, or a second one of its name: `{decl}`")
+        restype = _ctype(m[1].replace("*", " * ").split(), None, decl)
+        params = [] if m[3].strip() == "void" else [p.replace("*", " * ").split() or [""] for p in m[3].split(",")]
+        signatures[m[2]] = (restype, [_ctype(p[:-1], p[-1], decl) for p in params])         # the last identifier is the name
+    return signatures, constants
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise UavGnnError(f"{HEADER_PATH} is missing ({e}): the ctypes table and the UAVGNN_* constants are read from the header") from e
+
+
+# name -> (restype, argtypes), and every UAVGNN_* integer macro (error codes, GEMM epilogue / variant bits, TD-return and workspace
+# kinds) as an attribute of this module.  tests/test_cabi_symbols.py pins a set of entries by hand against this reading.
+SIGNATURES, _CONSTANTS = _read_header()
+globals().update(_CONSTANTS)
+
+_LIB = None
 
 
 def lib() -> ctypes.CDLL:

@@ -700,14 +700,18 @@ GEMM_X3 = os.environ.get("UAVGNN_GEMM_X3", "1") != "0"   # False: vendor fp32 GE
 # A/B variants of the bf16x3 kernels are PER-CALL flag words of the C ABI (include/uavgnn.h: the library keeps no process-wide
 # state); the probes set these module attributes, the environment seeds them: GEMM 8 (default) / 9 (staging interleaved) / 4
 # (128 x 128 tiles), GRU cell 1 (default: staging interleaved) / 0 (staging in blocks)
-GEMM_X3_FLAGS = {"8": 0, "9": 4, "4": 8}.get(os.environ.get("UAVGNN_GEMM_X3_VARIANT", "8"), 0)
-GRU_X3_FLAGS = 1 if os.environ.get("UAVGNN_GRU_X3_VARIANT", "1") == "0" else 0
+GEMM_X3_FLAGS = {"8": 0, "9": L.UAVGNN_GEMM_STAGING_INTERLEAVED, "4": L.UAVGNN_GEMM_TILE_128}.get(os.environ.get("UAVGNN_GEMM_X3_VARIANT", "8"), 0)
+GRU_X3_FLAGS = L.UAVGNN_GRU_STAGING_BLOCKS if os.environ.get("UAVGNN_GRU_X3_VARIANT", "1") == "0" else 0
 
 
 GEMM_X3_SMALL_GRID = 128   # fewer 256 x 128 tiles than this: 128 x 128 tiles instead
 
 
 GEMM_X3_MIN_ROWS = 4096   # fewer rows: the vendor GEMM
+
+
+def _gemm_epilogue(accumulate, relu) -> int:
+    return (L.UAVGNN_GEMM_ACCUMULATE if accumulate else 0) | (L.UAVGNN_GEMM_RELU if relu else 0)
 
 
 def gemm_x3_supported(a, n_out, k) -> bool:
@@ -732,14 +736,15 @@ def gemm_x3(a, W, transpose_w=False, bias=None, out=None, accumulate=False, relu
                                 lambda p: L.check(lib.uavgnn_split_bf16x3(W.data_ptr(), W.stride(0), R, C, int(transpose_w),
                                                                           p.data_ptr(), L.stream()), "uavgnn_split_bf16x3"))
         flags = GEMM_X3_FLAGS
-        if not (flags & 8) and ((M + 255) // 256) * ((n_out + 127) // 128) < GEMM_X3_SMALL_GRID:
+        if not (flags & L.UAVGNN_GEMM_TILE_128) and ((M + 255) // 256) * ((n_out + 127) // 128) < GEMM_X3_SMALL_GRID:
             # C2-size batches (N_a = 4096): the 256 x 128 tiles of the eight-wave kernel are 32 workgroups on 256 CUs (58 us for
             # [4096, 768] x [768, 256]); the four-wave kernel's 128 x 128 tiles double the workgroups (UAVGNN_GEMM_TILE_128)
-            flags |= 8
+            flags |= L.UAVGNN_GEMM_TILE_128
             if ((M + 127) // 128) * ((n_out + 127) // 128) < GEMM_X3_SMALL_GRID:
-                flags = (flags & ~8) | 16         # still under half the CUs: 64 x 128 tiles (UAVGNN_GEMM_TILE_64)
-        epi = (1 if accumulate else 0) | (2 if relu else 0) | flags
-        if rowmax_out is not None and not (flags & 24):      # ... + max |.| over every row of `a`, a by-product of the staging
+                flags = (flags & ~L.UAVGNN_GEMM_TILE_128) | L.UAVGNN_GEMM_TILE_64         # still under half the CUs: 64 x 128 tiles
+        epi = _gemm_epilogue(accumulate, relu) | flags
+        # ... + max |.| over every row of `a`, a by-product of the staging (the 256 x 128-tile kernel only)
+        if rowmax_out is not None and not (flags & (L.UAVGNN_GEMM_TILE_128 | L.UAVGNN_GEMM_TILE_64)):
             rc = lib.uavgnn_gemm_nt_x3_rowmax(a.data_ptr(), a.stride(0), M, K, planes.data_ptr(), n_out, L.ptr(bias), out.data_ptr(),
                                               out.stride(0), epi, rowmax_out.data_ptr(), L.stream())
         else:
@@ -777,7 +782,7 @@ def gemm_x3_cat_supported(a1, a2, n_out) -> bool:
     return bool(a2.is_cuda and a2.dtype == th.float32 and a2.dim() == 2 and a2.shape[0] == a1.shape[0] and K1 % 32 == 0
                 and K2 % 32 == 0 and _mc_operand(a2)
                 and a2.shape[0] * a2.stride(0) < 2 ** 31 and gemm_x3_supported(a1, n_out, K1 + K2)
-                and ((a1.shape[0] + 255) // 256) * ((n_out + 127) // 128) >= GEMM_X3_SMALL_GRID and not (GEMM_X3_FLAGS & 8))
+                and ((a1.shape[0] + 255) // 256) * ((n_out + 127) // 128) >= GEMM_X3_SMALL_GRID and not (GEMM_X3_FLAGS & L.UAVGNN_GEMM_TILE_128))
 
 
 def gemm_x3_cat(a1, a2, W1, W2, out):
@@ -796,7 +801,7 @@ def gemm_x3_cat(a1, a2, W1, W2, out):
     with KERNEL_TIMER.span("gemm_x3", (M, n_out, K)):
         planes = _weight_planes("matcat", (W1, W2), (K1, K2, n_out), 6 * K * n_out, build)
         rc = lib.uavgnn_gemm_nt_x3_cat(a1.data_ptr(), a1.stride(0), K1, a2.data_ptr(), a2.stride(0), M, K, planes.data_ptr(), n_out,
-                                       None, out.data_ptr(), out.stride(0), GEMM_X3_FLAGS & 4, L.stream())
+                                       None, out.data_ptr(), out.stride(0), GEMM_X3_FLAGS & L.UAVGNN_GEMM_STAGING_INTERLEAVED, L.stream())
     L.check(rc, "uavgnn_gemm_nt_x3_cat")
     return out
 
@@ -845,7 +850,7 @@ def gemm_h2(a, W, rowmax, transpose_w=False, bias=None, out=None, accumulate=Fal
         fn, rm2 = (lib.uavgnn_gemm_nt_h2, rowmax2) if rowmax2_out is None else (lib.uavgnn_gemm_nt_h2_rm2, rowmax2_out)
         rc = fn(a.data_ptr(), a.stride(0), K1, L.ptr(a2), 0 if a2 is None else a2.stride(0), M, K, rowmax.data_ptr(),
                 L.ptr(rm2), planes.data_ptr(), n_out, L.ptr(bias), out.data_ptr(), out.stride(0),
-                (1 if accumulate else 0) | (2 if relu else 0) | (GEMM_X3_FLAGS & 4), L.stream())
+                _gemm_epilogue(accumulate, relu) | (GEMM_X3_FLAGS & L.UAVGNN_GEMM_STAGING_INTERLEAVED), L.stream())
     L.check(rc, "uavgnn_gemm_nt_h2")
     return out
 
@@ -1215,7 +1220,7 @@ class _TdReturnLoss(th.autograd.Function):
         g = th.empty((T, B, C), dtype=th.float32, device=dev)
         loss = th.empty((), dtype=th.float32, device=dev)
         kind, p = returns
-        mode, n_step, lam = (0, p, 0.0) if kind == "nstep" else (1, 0, p)
+        mode, n_step, lam = (L.UAVGNN_TD_NSTEP, p, 0.0) if kind == "nstep" else (L.UAVGNN_TD_LAMBDA, 0, p)
         with KERNEL_TIMER.span("td_return_fwd", (T, B, C)):
             rc = lib.uavgnn_td_return_fwd(qvals.data_ptr(), next_vals.data_ptr(), rews.data_ptr(), Cr, dones.data_ptr(), L.ptr(weights), T, B,
                                           C, float(gamma), mode, n_step, lam, td.data_ptr(), g.data_ptr(), loss.data_ptr(),
