@@ -17,6 +17,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # UAVGNN_LIB: another build of the same library (kernel A/Bs of the probes: a variant compiled with different -D switches)
 LIB_PATH = os.environ.get("UAVGNN_LIB") or os.path.join(_HERE, "csrc", "libuavgnn.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "uavgnn.h")   # the include directory build.py compiles against
+# the second shared object: entry points that replace no reference call site (include/uavgnn_ext.h, csrc/ext/*.hip)
+EXT_LIB_PATH = os.environ.get("UAVGNN_EXT_LIB") or os.path.join(_HERE, "csrc", "libuavgnn_ext.so")
+EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "uavgnn_ext.h")
 
 
 class UavGnnError(RuntimeError):
@@ -65,20 +68,24 @@ def parse_header(text: str):
     return signatures, constants
 
 
-def _read_header():
+def _read_header(path=None):
+    path = HEADER_PATH if path is None else path
     try:
-        with open(HEADER_PATH) as f:
+        with open(path) as f:
             return parse_header(f.read())
     except OSError as e:
-        raise UavGnnError(f"{HEADER_PATH} is missing ({e}): the ctypes table and the UAVGNN_* constants are read from the header") from e
+        raise UavGnnError(f"{path} is missing ({e}): the ctypes table and the UAVGNN_* constants are read from the header") from e
 
 
 # name -> (restype, argtypes), and every UAVGNN_* integer macro (error codes, GEMM epilogue / variant bits, TD-return and workspace
 # kinds) as an attribute of this module.  tests/test_cabi_symbols.py pins a set of entries by hand against this reading.
 SIGNATURES, _CONSTANTS = _read_header()
 globals().update(_CONSTANTS)
+# the same reading of include/uavgnn_ext.h; it defines no constant of its own (the error codes are the main library's)
+EXT_SIGNATURES = _read_header(EXT_HEADER_PATH)[0]
 
 _LIB = None
+_EXT = None
 
 
 def lib() -> ctypes.CDLL:
@@ -101,6 +108,21 @@ def lib() -> ctypes.CDLL:
             from .tuned import enable_tuned_gemms
             enable_tuned_gemms()
     return _LIB
+
+
+def ext() -> ctypes.CDLL:
+    """Loads libuavgnn_ext.so once (``build.build_lib`` builds it beside the main library).  Fails loudly when it is missing."""
+    global _EXT
+    if _EXT is None:
+        if not os.path.exists(EXT_LIB_PATH):
+            raise UavGnnError(f"{EXT_LIB_PATH} is missing - build it with `python -c 'import __graft_entry__ as g; "
+                              f"g.build()'`.  uav_bs_ctrl_amd has no CPU / eager fallback.")
+        handle = ctypes.CDLL(EXT_LIB_PATH)
+        for name, (res, args) in EXT_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = res, args
+        _EXT = handle
+    return _EXT
 
 
 def check(code: int, what: str) -> None:

@@ -16,7 +16,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..graph import FlatObsBatch, HeteroBatch, RelationView
-from .heads import DuelingLayer
+from .heads import DuelingLayer, NoisyLinear, build_head
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -124,7 +124,7 @@ def _gru(cell: nn.GRUCell, i_parts, h):
 
 def _head(f_out, h):
     """Q head (gnn_agents.py:43-46,:56)."""
-    if isinstance(f_out, DuelingLayer):
+    if isinstance(f_out, (DuelingLayer, NoisyLinear)):      # (a NoisyLinear in its mode "off" is the plain head on its means)
         return f_out(h)
     return ops.linear(h, f_out.weight, f_out.bias)
 
@@ -347,10 +347,7 @@ class GnnAgent(nn.Module):
         else:
             raise KeyError("Unsupported communication scheme.")
 
-        if args.dueling:
-            self.f_out = DuelingLayer(self._hidden_size, n_actions)
-        else:
-            self.f_out = nn.Linear(self._hidden_size, n_actions)
+        self.f_out = build_head(self._hidden_size, n_actions, args)
 
     def init_hidden(self):
         return th.zeros(1, self._hidden_size)   # on CPU, as the reference does (gnn_agents.py:48-49)
@@ -409,7 +406,10 @@ class DrqnGnnAgent(nn.Module):
         d = self._hidden_size // self._n_heads
         self.enc = GATv2Conv((obs_shape["gt"], obs_shape["agent"]), d, self._n_heads)
         self.rnn = nn.GRUCell(self._hidden_size, self._hidden_size)
-        self.f_out = nn.Linear(self._hidden_size, n_actions)
+        if getattr(args, "dueling", False) and getattr(args, "noisy", None) is None:
+            self.f_out = nn.Linear(self._hidden_size, n_actions)       # the DRQN agent has no dueling form (drqn/agents/gnn_agents.py:17)
+        else:
+            self.f_out = build_head(self._hidden_size, n_actions, args)
 
     def init_hidden(self):
         return th.zeros(1, self._hidden_size)
@@ -426,7 +426,7 @@ class DrqnGnnAgent(nn.Module):
         if h.shape[0] != n:
             h = h.expand(n, -1)
         h = _gru(self.rnn, (x,), h.contiguous())
-        return ops.linear(h, self.f_out.weight, self.f_out.bias), h
+        return _head(self.f_out, h), h
 
     def unroll(self, x_all, h0, T1):
         """q_all [T1, N, n_actions] from the pre-encoded observations of T1 time-major steps."""

@@ -17,7 +17,7 @@ import torch.nn as nn
 
 from ..graph import FlatObsBatch, HeteroBatch
 from .gnn_agents import _gru, _head, _unroll, mlp_encode
-from .heads import DuelingLayer
+from .heads import build_head
 
 
 class RnnAgent(nn.Module):
@@ -32,10 +32,7 @@ class RnnAgent(nn.Module):
             layers += [nn.Linear(self._hidden_size, self._hidden_size), nn.ReLU()]
         self.enc = nn.Sequential(*layers)
         self.rnn = nn.GRUCell(self._hidden_size, self._hidden_size)
-        if args.dueling:
-            self.f_out = DuelingLayer(self._hidden_size, n_actions)
-        else:
-            self.f_out = nn.Linear(self._hidden_size, n_actions)
+        self.f_out = build_head(self._hidden_size, n_actions, args)
 
     def init_hidden(self):
         return th.zeros(1, self._hidden_size)   # on CPU, as the reference does (rnn_agents.py:27-29)

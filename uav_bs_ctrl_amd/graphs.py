@@ -202,7 +202,8 @@ class _GraphedActBase:
 
     @th.no_grad()
     def _body(self):
-        logits, h = self.learner.policy_net(self._obs(), self.h_in)
+        with self.learner.rollout_noise():
+            logits, h = self.learner.policy_net(self._obs(), self.h_in)
         return _select(self.learner, logits, self.eps), h
 
     def _replay(self, h, eps_thres: float):
@@ -645,7 +646,8 @@ class Episode(_EnvObs):
             rb.stage_obs(staged)
         L.check(L.lib().uavgnn_eps_schedule(self.t.data_ptr(), E, self.eps_start, self.eps_end, self.decay_steps,
                                             self.eps.data_ptr(), L.stream()), "uavgnn_eps_schedule")
-        logits, h2 = lr.policy_net(self._obs(), h)
+        with lr.rollout_noise():
+            logits, h2 = lr.policy_net(self._obs(), h)
         acts = _select(lr, logits, self.eps, self.explore)
         o2, rew, done, info = env.step(acts)
         if self.single:

@@ -17,6 +17,8 @@ exchange is one all-reduce (RCCL over xGMI; ``nccl`` backend) of the Q-network g
 """
 from __future__ import annotations
 
+import contextlib
+import copy
 from typing import Dict, List, Optional
 
 import torch as th
@@ -26,6 +28,7 @@ import torch.nn.functional as F
 from . import _lib as L
 from . import ops
 from .agents import REGISTRY as agent_REGISTRY
+from .agents.heads import noisy_heads, noisy_mode
 
 
 class FlatGradBuffer:
@@ -87,9 +90,17 @@ def broadcast_parameters(module: th.nn.Module, src: int = 0, group=None, force: 
 class MultiAgentQLearner:
     """returns: the TD target of ``update`` - None (the reference's one-step target, learner.py:150; every launch as it was),
     ``("nstep", n)`` with an integer n >= 1 or ``("lambda", lam)`` with 0 <= lam <= 1: multi-step targets over the stored sequence
-    (``ops.td_return_loss``; DESIGN "Multi-step TD targets")."""
+    (``ops.td_return_loss``; DESIGN "Multi-step TD targets").
+    noisy: None (the plain / dueling head; every launch as it was) or sigma0, a number: the noisy-net Q head (agents/heads.py
+    ``NoisyLinear``; DESIGN "Noisy-net exploration") - ``act`` and the rollout steps of ``graphs`` draw per row (``rollout_noise``),
+    ``loss`` folds one draw per network, evaluations use the means.  The caller's ``args`` object is left as it is."""
 
-    def __init__(self, env_info: dict, args, process_group=None, returns=None):
+    def __init__(self, env_info: dict, args, process_group=None, returns=None, noisy=None):
+        if noisy is not None:
+            if isinstance(noisy, bool) or not isinstance(noisy, (int, float)):
+                raise ValueError(f"noisy: sigma0 must be a number, got {noisy!r}")
+            args = copy.copy(args)
+            args.noisy = float(noisy)
         self.args = args
         self.returns = ops.normalize_returns(returns)
         self._td_workspace = {}       # ops.td_return_loss: the loss's partial sums, one buffer per shape (fixed addresses under capture)
@@ -107,6 +118,7 @@ class MultiAgentQLearner:
         for p in self.target_net.parameters():
             p.requires_grad_(False)
         self.params = list(self.policy_net.parameters())
+        self._noisy_policy, self._noisy_target = noisy_heads(self.policy_net), noisy_heads(self.target_net)
         self.mixer = None
         if getattr(args, "mixer", False):   # QMIX (learner.py:35-40); every launcher of the reference sets mixer=False
             from copy import deepcopy
@@ -170,6 +182,11 @@ class MultiAgentQLearner:
         return h0.expand(self.n_agents * batch_size, -1).contiguous()
 
     # ---- rollout --------------------------------------------------------------------------------------------------
+    def rollout_noise(self):
+        """The scope of a TRAINING rollout step: the policy's noisy heads draw per row (nothing without the option).  Evaluations do
+        not enter it: they use the means."""
+        return noisy_mode(self._noisy_policy, "rows") if self._noisy_policy else contextlib.nullcontext()
+
     @th.no_grad()
     def act(self, obs, h: th.Tensor, eps_thres: float):
         """obs: HeteroBatch of B envs (B*n agents).  Returns (acts [B*n] int64 on device, h').  One epsilon draw per
@@ -186,7 +203,7 @@ class MultiAgentQLearner:
             if fp != self._rollout_fingerprint:
                 self._rollout_planes.clear()
                 self._rollout_fingerprint = fp
-        with ops.frozen_weights(self._rollout_planes):
+        with ops.frozen_weights(self._rollout_planes), self.rollout_noise():
             logits, h = self.policy_net(obs, h)
         N = logits.shape[0]
         B = N // self.n_agents
@@ -246,7 +263,14 @@ class MultiAgentQLearner:
         """Forward part of ``update`` (learner.py:110-154).  batch: obs (list of T+1 HeteroBatch of B envs each),
         h0 / h1 [B*n, H] (stored hidden states of the first two steps), acts [T, B*n, 1] int64,
         rews [T, B, n or 1], dones [T, B, 1]; optional obs_all = the T+1 observation graphs batched in time-major
-        order (``graph.batch(obs)``), which switches on the time-batched encoder."""
+        order (``graph.batch(obs)``), which switches on the time-batched encoder.
+        With the noisy head each network folds ONE draw at its own pair here and uses it for all its steps of this call."""
+        if not self._noisy_policy:
+            return self._loss(batch)
+        with noisy_mode(self._noisy_policy, "shared"), noisy_mode(self._noisy_target, "shared"):
+            return self._loss(batch)
+
+    def _loss(self, batch: Dict) -> tuple:
         obs = batch["obs"]
         T = len(obs) - 1
         h, h_targ = batch["h0"], batch["h1"]
@@ -494,15 +518,14 @@ class QLearner(MultiAgentQLearner):
     such switch), ``double_q`` and ``mixer`` are not read.  The caller's ``args`` object is left as it is.  returns: passed through to
     the parent (multi-step targets on ``max`` bootstrap values, C = 1)."""
 
-    def __init__(self, env_info: dict, args, process_group=None, returns=None):
-        import copy
+    def __init__(self, env_info: dict, args, process_group=None, returns=None, noisy=None):
         args = copy.copy(args)
         if not hasattr(args, "dueling"):
             args.dueling = False
         args.double_q, args.mixer = False, False
         info = dict(env_info)
         info["n_agents"] = 1
-        super().__init__(info, args, process_group, returns)
+        super().__init__(info, args, process_group, returns, noisy)
 
     def _build_agent(self):
         """learner.py:48-52: an integer observation size -> 'rnn' (flattened observations), a dict of feature sizes -> the

@@ -1748,11 +1748,128 @@ def _duel_weff(W_adv, w_v):
     return _weight_planes("duel", (W_adv, w_v), (A, H), 4 * A * H, build).view(th.float32).view(A, H)
 
 
-def head_fwd(h, W_out, b_out, duel=None):
+# ---------------------------------------------------------------------------------------------------------------------
+# Noisy-net Q head (csrc/ext/noisy_head.hip, include/uavgnn_ext.h): W = W_mu + W_sigma (.) (f_out f_in^T), b = b_mu + b_sigma (.) f_out
+# ---------------------------------------------------------------------------------------------------------------------
+def noisy_f(z):
+    """f(z) = sign(z) sqrt|z| of the factorised noise."""
+    return z.sign() * z.abs().sqrt()
+
+
+def noisy_supported(h, W_mu, W_sigma, b_mu, b_sigma) -> bool:
+    """csrc/ext/noisy_head.hip has the per-row launch for this call: CUDA fp32, H in {64, 128, 256}, n_actions <= 16."""
+    return bool(h.is_cuda and h.dtype == th.float32 and h.dim() == 2 and h.shape[0] > 0 and _mc_operand(h)
+                and all(t.is_cuda and t.dtype == th.float32 for t in (W_mu, W_sigma, b_mu, b_sigma))
+                and _mc_operand(W_mu) and _mc_operand(W_sigma) and W_mu.stride(0) == W_sigma.stride(0)
+                and b_mu.is_contiguous() and b_sigma.is_contiguous()
+                and L.ext().uavgnn_noisy_head_supported(h.shape[1], W_mu.shape[0]))
+
+
+def noisy_noise(rng, N, H, A):
+    """(f_in [N, H], f_out [N, A]): the values f(xi) of the stream at the device pair `rng`, as the kernels use them (tests, probes)."""
+    L.require_gpu(rng)
+    f_in = th.empty((N, H), dtype=th.float32, device=rng.device)
+    f_out = th.empty((N, A), dtype=th.float32, device=rng.device)
+    L.check(L.ext().uavgnn_noisy_noise(rng.data_ptr(), N, H, A, f_in.data_ptr(), f_out.data_ptr(), L.stream()), "uavgnn_noisy_noise")
+    return f_in, f_out
+
+
+def _noisy_head_torch(h, W_mu, b_mu, W_sigma, b_sigma, f_in, f_out):
+    """The per-row draw in torch, in the kernel's order: (h W_mu^T + b_mu) + f_out (.) ((h (.) f_in) W_sigma^T + b_sigma)."""
+    return th.addmm(b_mu, h, W_mu.t()) + f_out * th.addmm(b_sigma, h * f_in, W_sigma.t())
+
+
+def noisy_fold_torch(W_mu, W_sigma, b_mu, b_sigma, f_in, f_out):
+    """(W_eff, b_eff) of one shared draw f_in [H], f_out [A], in the kernel's order (differentiable torch)."""
+    return W_mu + W_sigma * (f_out[:, None] * f_in[None, :]), b_mu + b_sigma * f_out
+
+
+class _NoisyFold(th.autograd.Function):
+    """(W_eff, b_eff, f_in, f_out) of ONE draw - row 0 of the stream at the pair `rng` - in one launch (uavgnn_noisy_fold); the backward
+    is one launch too (uavgnn_noisy_fold_bwd): the means' gradients are the incoming ones, the sigmas' are those times the noise."""
+
+    @staticmethod
+    def forward(ctx, W_mu, W_sigma, b_mu, b_sigma, rng):
+        L.require_gpu(W_mu, W_sigma, b_mu, b_sigma, rng)
+        A, H = W_mu.shape
+        W_mu, W_sigma, b_mu, b_sigma = L.f32c(W_mu), L.f32c(W_sigma), L.f32c(b_mu), L.f32c(b_sigma)
+        W_eff = th.empty((A, H), dtype=th.float32, device=W_mu.device)
+        b_eff, f_out = th.empty_like(b_mu), th.empty_like(b_mu)
+        f_in = th.empty((H,), dtype=th.float32, device=W_mu.device)
+        with KERNEL_TIMER.span("noisy_fold", (A, H)):
+            rc = L.ext().uavgnn_noisy_fold(W_mu.data_ptr(), W_sigma.data_ptr(), H, b_mu.data_ptr(), b_sigma.data_ptr(), A, H, rng.data_ptr(),
+                                           W_eff.data_ptr(), b_eff.data_ptr(), f_in.data_ptr(), f_out.data_ptr(), L.stream())
+        L.check(rc, "uavgnn_noisy_fold")
+        ctx.save_for_backward(f_in, f_out)
+        ctx.mark_non_differentiable(f_in, f_out)
+        return W_eff, b_eff, f_in, f_out
+
+    @staticmethod
+    def backward(ctx, dW, db, _d_in, _d_out):
+        f_in, f_out = ctx.saved_tensors
+        dWs, dbs = noisy_fold_bwd(dW, db, f_in, f_out)
+        return dW, dWs, db, dbs, None
+
+
+def noisy_fold_bwd(dW_eff, db_eff, f_in, f_out):
+    """(d W_sigma, d b_sigma) = (d W_eff (.) (f_out f_in^T), d b_eff (.) f_out); either gradient may be None (zeros then)."""
+    A, H = f_out.shape[0], f_in.shape[0]
+    if dW_eff is None:
+        dW_eff = th.zeros((A, H), dtype=f_in.dtype, device=f_in.device)
+    if db_eff is None:
+        db_eff = th.zeros((A,), dtype=f_in.dtype, device=f_in.device)
+    if not (f_in.is_cuda and f_in.dtype == th.float32):
+        return dW_eff * (f_out[:, None] * f_in[None, :]), db_eff * f_out
+    dW_eff = dW_eff if dW_eff.stride(1) == 1 and dW_eff.dtype == th.float32 else L.f32c(dW_eff.float())
+    db_eff = L.f32c(db_eff)
+    dWs, dbs = th.empty((A, H), dtype=th.float32, device=f_in.device), th.empty((A,), dtype=th.float32, device=f_in.device)
+    with KERNEL_TIMER.span("noisy_fold_bwd", (A, H)):
+        rc = L.ext().uavgnn_noisy_fold_bwd(dW_eff.data_ptr(), dW_eff.stride(0), db_eff.data_ptr(), f_in.data_ptr(), f_out.data_ptr(), A, H,
+                                           dWs.data_ptr(), dbs.data_ptr(), L.stream())
+    L.check(rc, "uavgnn_noisy_fold_bwd")
+    return dWs, dbs
+
+
+def noisy_fold(W_mu, W_sigma, b_mu, b_sigma, rng=None, noise=None):
+    """Mode "shared" of the noisy head: (W_eff, b_eff, f_in, f_out) of one draw, with autograd into the four parameters.
+    CUDA fp32 with a device pair `rng` and no injected noise: uavgnn_noisy_fold / uavgnn_noisy_fold_bwd (the step is NOT advanced here).
+    Elsewhere - CPU, float64, ``noise`` = (f_in [H], f_out [A]) injected (tests) - the same formula in torch, the draw from
+    ``torch.randn`` when none is given."""
+    A, H = W_mu.shape
+    if noise is None and rng is not None and W_mu.is_cuda and W_mu.dtype == th.float32:
+        return _NoisyFold.apply(W_mu, W_sigma, b_mu, b_sigma, rng)
+    if noise is None:
+        noise = (noisy_f(th.randn(H, dtype=W_mu.dtype, device=W_mu.device)), noisy_f(th.randn(A, dtype=W_mu.dtype, device=W_mu.device)))
+    f_in, f_out = noise
+    return (*noisy_fold_torch(W_mu, W_sigma, b_mu, b_sigma, f_in, f_out), f_in, f_out)
+
+
+def head_fwd(h, W_out, b_out, duel=None, noisy=None):
     """q = h W_out^T + b_out (gnn_agents.py:56), no autograd: csrc/head.hip for n_actions <= 16, else the vendor GEMM.
     duel = (W_adv, b_adv, w_v, b_v): the dueling head (dueling.py:13-16) instead - W_out / b_out are not read -, csrc/head.hip for
-    n_actions <= 15, else the torch formulation."""
+    n_actions <= 15, else the torch formulation.
+    noisy = (W_sigma, b_sigma, rng): the noisy head with one draw PER ROW (W_out / b_out are the means) - rng a device int64 pair
+    {seed, step}: ONE launch of csrc/ext/noisy_head.hip where it has the shape (the step is not advanced here: the caller does); rng a
+    tuple (f_in [N, H], f_out [N, A]) of injected noise, another shape, the CPU or float64: the torch formulation, its draw from
+    ``torch.randn`` unless injected."""
     N, H = h.shape
+    if noisy is not None:
+        Ws, bs, rng = noisy
+        A = W_out.shape[0]
+        if isinstance(rng, th.Tensor) and noisy_supported(h, W_out, Ws, b_out, bs):
+            q = th.empty((N, A), dtype=th.float32, device=h.device)
+            with KERNEL_TIMER.span("noisy_head_fwd", (N, H, A)):
+                rc = L.ext().uavgnn_noisy_head_fwd(h.data_ptr(), h.stride(0), N, H, W_out.data_ptr(), Ws.data_ptr(), W_out.stride(0),
+                                                   b_out.data_ptr(), bs.data_ptr(), A, rng.data_ptr(), q.data_ptr(), A, L.stream())
+            L.check(rc, "uavgnn_noisy_head_fwd")
+            return q
+        if isinstance(rng, tuple):
+            f_in, f_out = rng
+        elif isinstance(rng, th.Tensor) and rng.is_cuda and h.is_cuda:       # the stream's own values (other shapes on the GPU)
+            f_in, f_out = (t.to(h.dtype) for t in noisy_noise(rng, N, H, A))
+        else:
+            f_in, f_out = noisy_f(th.randn(N, H, dtype=h.dtype, device=h.device)), noisy_f(th.randn(N, A, dtype=h.dtype, device=h.device))
+        return _noisy_head_torch(h, W_out, b_out, Ws, bs, f_in, f_out)
     if duel is not None:
         Wa, ba, wv, bv = duel
         A = Wa.shape[0]
@@ -1814,9 +1931,12 @@ class _TarmacStep(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, h, Wp, bp, W_ih, b_ih, W_hh, b_hh, W_out, b_out, M, K, talk_off, talk_src, t_off, t_dst, t_pos,
-                split, env=None, dx_out=None, train=True, duel=None):
+                split, env=None, dx_out=None, train=True, duel=None, noisy=None):
         # duel = (W_adv, b_adv, w_v, b_v, identity): the dueling head (dueling.py:13-16) - the forward reads the four parameters in
         # csrc/head.hip; W_out / b_out are then the fold W_eff / b_eff (``dueling_fold``), which is all the backward needs
+        # noisy: the noisy head (agents/heads.py NoisyLinear) - ("shared", identity): W_out / b_out are the fold of this update's draw
+        # (``noisy_fold``), a plain head to forward and backward, its gradient sunk under the module's identity; ("rows", W_sigma,
+        # b_sigma, rng): a no-grad rollout step, W_out / b_out the means, one draw per row inside the head launch
         L.require_gpu(x, h, Wp, W_ih, talk_off)
         N, H = x.shape
         x, h = L.f32c(x), L.f32c(h)
@@ -1906,8 +2026,11 @@ class _TarmacStep(th.autograd.Function):
                 L.check(rc, "uavgnn_gru_gates_fwd")
             # (an accepted step that ran unfused wrote h' into a tensor of its own, not into slot t + 1: the next step's h then
             # fails the slot check above and reduces per step, like this one - ctx.seq stays None)
-        q = head_fwd(h2, W_out, b_out, None if duel is None else duel[:4])
+        rows = noisy is not None and noisy[0] == "rows"
+        q = head_fwd(h2, W_out, b_out, None if duel is None else duel[:4], noisy[1:] if rows else None)
         ctx.out_id = None if duel is None else duel[4]
+        if noisy is not None and not rows:
+            ctx.out_id = noisy[1]
         if proj is None:
             proj = h2                                              # no-grad call through the fused message launch: placeholder
         ctx.dims = (M, K)
@@ -1945,7 +2068,7 @@ class _TarmacStep(th.autograd.Function):
             gWih, gbih = _wgrad(d_gi, inp), _colsum(d_gi)
             gWhh, gbhh = _wgrad(d_gh, h), th.cat((gbih[:2 * H], _colsum(d_gh[:, 2 * H:])))
             gWo, gbo = _wgrad(dq, h2), _colsum(dq)
-        return (dx, dh, gWp, gbp, gWih, gbih, gWhh, gbhh, gWo, gbo) + (None,) * 12
+        return (dx, dh, gWp, gbp, gWih, gbih, gWhh, gbhh, gWo, gbo) + (None,) * 13
 
 
 def _step_dh2(fused_gru, sink, dq, dh2, W_out, N, H):
@@ -2074,8 +2197,8 @@ def _step_input_grads(seq, t, sink, dims, env, dx_out, proj, a_save, Wp, W_ih, W
 
 
 def tarmac_step(x, h, g, comm, f_out, stacked=None, dx_out=None):
-    """comm: the TarMAC module (f_val / f_sign / f_que / f_udt), f_out: nn.Linear head or a DuelingLayer (the caller checks
-    ``dueling_supported``).  Returns (q, h').
+    """comm: the TarMAC module (f_val / f_sign / f_que / f_udt), f_out: nn.Linear head, a DuelingLayer (the caller checks
+    ``dueling_supported``) or a NoisyLinear in any of its modes (agents/heads.py: "off" is the plain head on its means).  Returns (q, h').
     ``stacked`` = (Wp, bp) built WITH autograd history when no GRAD_SINK will collect the weight gradients."""
     M, K = comm._msg_size, comm._key_size
     Wp, bp = stacked if stacked is not None else comm.fused_projection()
@@ -2083,6 +2206,8 @@ def tarmac_step(x, h, g, comm, f_out, stacked=None, dx_out=None):
     cell = comm.f_udt
     dueling = hasattr(f_out, "adv_head")
     head_params = dueling_params(f_out) if dueling else (f_out.weight, f_out.bias)
+    noisy_mode = getattr(f_out, "noisy_mode", "off")
+    fold = f_out.fold() if noisy_mode == "shared" else None     # this update's draw: (W_eff, b_eff) stand in for the plain head's pair
     env = _talk_env(g, M, K)
     t_off, t_dst, t_pos = ((None, None, None) if env is not None else
                            _talk_transpose_if_needed(g, x, h, Wp, cell.weight_ih, head_params[0]))
@@ -2122,6 +2247,20 @@ def tarmac_step(x, h, g, comm, f_out, stacked=None, dx_out=None):
                 _, dba, _, dbv = dueling_split(None, grad)
                 _add_grad(ba, dba)
                 _add_grad(bv, dbv)
+        elif fold is not None and name in ("W_out", "b_out"):
+            # d W_eff / d b_eff of THIS fold (the slot is keyed by it): the means' gradients as they are; the sigmas' are those times the
+            # fold's noise - one launch once both halves are in
+            _add_grad(params[name], grad)
+            if fold.done:
+                dWs, dbs = noisy_fold_bwd(grad if name == "W_out" else None, grad if name == "b_out" else None, fold.f_in, fold.f_out)
+            else:
+                fold.pending[name] = grad if name not in fold.pending else fold.pending[name] + grad
+                if len(fold.pending) < 2:
+                    return
+                dWs, dbs = noisy_fold_bwd(fold.pending.pop("W_out"), fold.pending.pop("b_out"), fold.f_in, fold.f_out)
+                fold.done = True
+            _add_grad(f_out.weight_sigma, dWs)
+            _add_grad(f_out.bias_sigma, dbs)
         else:
             _add_grad(params[name], grad)
 
@@ -2129,8 +2268,19 @@ def tarmac_step(x, h, g, comm, f_out, stacked=None, dx_out=None):
     # which reads the saved pre-activation sets
     train = th.is_grad_enabled() and any(t.requires_grad for t in (x, h, Wp, bp, cell.weight_ih, cell.bias_ih,
                                                                    cell.weight_hh, cell.bias_hh) + tuple(head_params))
-    duel = None
-    if not dueling:
+    duel = noisy = None
+    if noisy_mode == "rows":
+        if train:
+            raise L.UavGnnError("tarmac_step: the noisy head's mode 'rows' is the no-grad rollout form; an update runs in mode 'shared'")
+        W_out, b_out = head_params
+        noisy = ("rows", f_out.weight_sigma.detach(), f_out.bias_sigma.detach(), f_out.rng())
+    elif fold is not None:
+        if stacked is not None:     # no sink: autograd carries the gradients of the fold back to the four parameters
+            W_out, b_out = fold.W, fold.b
+        else:
+            W_out, b_out = fold.W.detach(), fold.b.detach()
+            noisy = ("shared", id(fold))
+    elif not dueling:
         W_out, b_out = head_params
     else:
         Wa, ba, wv, bv = head_params
@@ -2139,8 +2289,11 @@ def tarmac_step(x, h, g, comm, f_out, stacked=None, dx_out=None):
             W_out, b_out = dueling_fold(Wa, ba, wv, bv)
         else:                       # (a no-grad call has no backward: nothing reads W_out then)
             W_out, b_out = (_duel_weff(Wa, wv) if train else duel[0]), duel[1]
-    return _TarmacStep.apply(x, h, Wp, bp, cell.weight_ih, cell.bias_ih, cell.weight_hh, cell.bias_hh, W_out, b_out, M, K, off, src, t_off,
-                             t_dst, t_pos, split, env, dx_out, train, duel)
+    out = _TarmacStep.apply(x, h, Wp, bp, cell.weight_ih, cell.bias_ih, cell.weight_hh, cell.bias_hh, W_out, b_out, M, K, off, src, t_off,
+                            t_dst, t_pos, split, env, dx_out, train, duel, noisy)
+    if noisy_mode == "rows":
+        noisy[3][1:].add_(1)        # one launch consumed one step
+    return out
 
 
 class _DiscComm(th.autograd.Function):

@@ -38,7 +38,7 @@ import numpy as np
 from . import run as R
 from .run import RunDirectoryError
 
-MODEL_KEYS = ("o", "c", "agent", "hidden_size", "n_layers", "n_heads", "msg_size", "key_size", "n_rounds", "dueling")
+MODEL_KEYS = ("o", "c", "agent", "hidden_size", "n_layers", "n_heads", "msg_size", "key_size", "n_rounds", "dueling", "noisy")
 SUMMARY, SUMMARY_T, FIGURE = "test_summary.csv", "test_summary_t.csv", "test_summary.png"
 INFO_KEYS = ("EpRet", "EpLen", "AvgGlobalUtility", "TotalThroughput", "FairIdx", "ProbCollision")       # graphs.INFO_KEYS, without torch
 
@@ -133,6 +133,13 @@ def describe(run_dir: str, device="cuda") -> RunDescription:
     except ValueError as e:
         raise RunDirectoryError(f"{run_dir}: config.json's arguments are refused ({e})") from e
     ns.device, ns.mixer = str(device), False
+    if ours is not None and ours.get("noisy") is not None:
+        # the run trained the noisy-net Q head (``Run.create(noisy=sigma0)``): the learner builds it, the checkpoint's sigmas load into it,
+        # and the evaluation - like every evaluation - uses the means
+        try:
+            ns.noisy = R._noisy(ours["noisy"])
+        except ValueError as e:
+            raise RunDirectoryError(f"{run_dir}: config.json is unreadable: {e}") from e
     if exp == "exp1":
         enc = ns.agent
     else:
