@@ -70,6 +70,40 @@ def to_batch(g, device="cuda"):
     return HeteroBatch.from_arrays(**g).to(device)
 
 
+def _random_talk(N, max_deg, seed):
+    """Random CSC with in-degrees in [0, max_deg] (some zero), arbitrary sources; returns a HeteroBatch with talk only."""
+    from uav_bs_ctrl_amd import HeteroBatch
+    gen = th.Generator().manual_seed(seed)
+    deg = th.randint(0, max_deg + 1, (N,), generator=gen)
+    deg[0] = max_deg
+    deg[1] = 0
+    off = th.zeros(N + 1, dtype=th.int32)
+    off[1:] = th.cumsum(deg, 0).to(th.int32)
+    src = th.randint(0, N, (int(off[-1]),), generator=gen).to(th.int32)
+    return HeteroBatch.from_arrays(x_a=th.zeros(N, 2), talk_off=off, talk_src=src), off, src
+
+
+def _ragged_env_talk(sizes, p, seed):
+    """Batch of small graphs with random in-graph talk edges (simple graphs, CSC order).  Returns host arrays."""
+    gen = th.Generator().manual_seed(seed)
+    bounds = [0]
+    for k in sizes:
+        bounds.append(bounds[-1] + k)
+    N = bounds[-1]
+    src_l, dst_l = [], []
+    for gi, k in enumerate(sizes):
+        adj = th.rand(k, k, generator=gen) < (0.0 if gi % 5 == 3 else p)
+        i, j = adj.nonzero(as_tuple=True)
+        src_l.append(i + bounds[gi])
+        dst_l.append(j + bounds[gi])
+    src, dst = th.cat(src_l), th.cat(dst_l)
+    o = th.argsort(dst * N + src)
+    src, dst = src[o], dst[o]
+    off = th.zeros(N + 1, dtype=th.int32)
+    off[1:] = th.cumsum(th.bincount(dst, minlength=N), 0)
+    return N, off, src.to(th.int32), dst, bounds
+
+
 def default_init_params(cfg, seed=0, obs_shape=None):
     """state_dict of a freshly initialised agent (DGL-style init), as float64 CPU tensors for the oracle."""
     th.manual_seed(seed)

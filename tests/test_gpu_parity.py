@@ -7,8 +7,8 @@ import pytest
 import torch as th
 
 from oracle import restatement as R
-from tests.gpu_util import (EXP3, UPDATE_CASES, _exp3_learner_and_sequence, _LibSpy, _oracle_at_gpu_branch,
-                            agent_from_params, default_init_params, make_args, synth_graph, to_batch)
+from tests.gpu_util import (EXP3, UPDATE_CASES, _exp3_learner_and_sequence, _LibSpy, _oracle_at_gpu_branch, _ragged_env_talk,
+                            _random_talk, agent_from_params, default_init_params, make_args, synth_graph, to_batch)
 from tests.util import assert_close, grad_close, load_golden, load_learner_golden, wait_worker
 
 pytestmark = pytest.mark.gpu
@@ -413,19 +413,6 @@ def test_mfma_and_valu_kernels_agree_and_order_is_only_a_schedule():
     assert_close(sums[deg > 0], th.ones_like(sums[deg > 0]), 1e-6, "attention weights sum to one per destination")
 
 
-def _random_talk(N, max_deg, seed):
-    """Random CSC with in-degrees in [0, max_deg] (some zero), arbitrary sources; returns a HeteroBatch with talk only."""
-    from uav_bs_ctrl_amd import HeteroBatch
-    gen = th.Generator().manual_seed(seed)
-    deg = th.randint(0, max_deg + 1, (N,), generator=gen)
-    deg[0] = max_deg
-    deg[1] = 0
-    off = th.zeros(N + 1, dtype=th.int32)
-    off[1:] = th.cumsum(deg, 0).to(th.int32)
-    src = th.randint(0, N, (int(off[-1]),), generator=gen).to(th.int32)
-    return HeteroBatch.from_arrays(x_a=th.zeros(N, 2), talk_off=off, talk_src=src), off, src
-
-
 @pytest.mark.parametrize("N,max_deg,K,M", [(40, 150, 16, 64), (300, 9, 5, 200), (64, 70, 64, 256), (17, 3, 1, 1)])
 def test_talk_attention_kernel_vs_oracle(N, max_deg, K, M):
     """K3b alone, incl. in-degree > 64 (multi-pass), K / M at their limits, zero-in-degree nodes, duplicate edges."""
@@ -734,27 +721,6 @@ def test_csc_transpose_large_scan_and_empty(N):
                                  talk_src=th.zeros(0, dtype=th.int32), device="cuda")
     t_off, t_dst, t_pos = g0.talk_transpose()
     assert t_off.cpu().tolist() == [0] * 8 and t_dst.numel() == 0 and t_pos.numel() == 0
-
-
-def _ragged_env_talk(sizes, p, seed):
-    """Batch of small graphs with random in-graph talk edges (simple graphs, CSC order).  Returns host arrays."""
-    gen = th.Generator().manual_seed(seed)
-    bounds = [0]
-    for k in sizes:
-        bounds.append(bounds[-1] + k)
-    N = bounds[-1]
-    src_l, dst_l = [], []
-    for gi, k in enumerate(sizes):
-        adj = th.rand(k, k, generator=gen) < (0.0 if gi % 5 == 3 else p)
-        i, j = adj.nonzero(as_tuple=True)
-        src_l.append(i + bounds[gi])
-        dst_l.append(j + bounds[gi])
-    src, dst = th.cat(src_l), th.cat(dst_l)
-    o = th.argsort(dst * N + src)
-    src, dst = src[o], dst[o]
-    off = th.zeros(N + 1, dtype=th.int32)
-    off[1:] = th.cumsum(th.bincount(dst, minlength=N), 0)
-    return N, off, src.to(th.int32), dst, bounds
 
 
 @pytest.mark.parametrize("sizes,p,K,M", [([8] * 37, 1.0, 16, 64), ([1, 16, 3, 8, 2, 16, 5, 7, 9, 1, 1, 12], 0.5, 16, 64),

@@ -11,6 +11,8 @@ import os
 import pytest
 import torch as th
 
+from tests.k1_closed_form import float64_closed_form as _float64_closed_form
+
 pytestmark = pytest.mark.gpu
 
 H = 256
@@ -101,53 +103,6 @@ def test_resident_k1_backward_mixed_classes(monkeypatch, N, lo, hi, seed):
     _repeatable(run, lib.uavgnn_gatv2_bwd, g_new, 4)
     _agree(g_new, g_gen, "resident vs generic, mixed classes")
     _agree(g_new, _per_destination(monkeypatch, run, lib), "resident vs per-destination, mixed classes")
-
-
-def _float64_closed_form(data, deg, chunk=2048):
-    """The K1 backward of a relation with `deg` in-edges per destination, in float64 from the kernels' own fp32 inputs (the saved
-    attention included): g = d_out [out > 0]; de_uk = a_uk (G[k].x_u - T[k]); dz_un = de_uk attn[n] lrelu'(z_un).
-    Also, per gradient element, the most the (edge, channel) pairs with z within 2^-18 of the size of its terms can move it when
-    an fp32 evaluation of z takes the other side of zero (lrelu' jumps by 1 - slope there): the sign-tie allowance."""
-    x_src, x_dst, out, d_out, a_save, N = (data[k] for k in ("x_src", "x_dst", "out", "d_out", "a_save", "N"))
-    W_s, b_s, W_d, b_d, attn = (t.double() for t in data["prm"][:5])
-    acc = {nm: th.zeros(t.shape, dtype=th.float64, device=t.device) for nm, t in zip(NAMES, data["prm"])}
-    tie = {nm: th.zeros(t.shape, dtype=th.float64, device=t.device) for nm, t in zip(NAMES, data["prm"])}
-    Wk = W_s.view(4, 64, 4)
-    for s in range(0, N, chunk):
-        e = min(N, s + chunk)
-        n = e - s
-        x = x_src[s * deg:e * deg].double().view(n, deg, 4)
-        a = a_save[s * deg:e * deg].double().view(n, deg, 4)
-        xv = x_dst[s:e].double()
-        g = d_out[s:e, :H].double() * (out[s:e, :H] > 0)
-        G = th.einsum("nkd,kdf->nkf", g.view(n, 4, 64), Wk)
-        dot = th.einsum("nuf,nkf->nuk", x, G)
-        de = a * (dot - (a * dot).sum(1, keepdim=True))
-        c = xv @ W_d.T + b_d + b_s
-        z = th.einsum("nuf,hf->nuh", x, W_s) + c[:, None, :]
-        pos = z > 0
-        de_h = de.repeat_interleave(64, dim=2)
-        acc["dattn"] += (de_h * th.where(pos, z, SLOPE * z)).sum((0, 1))
-        dz = de_h * attn * th.where(pos, 1.0, SLOPE)
-        near = z.abs() <= 2.0 ** -18 * (th.einsum("nuf,hf->nuh", x.abs(), W_s.abs()) + c.abs()[:, None, :])
-        jump = (de_h * attn).abs() * (1 - SLOPE) * near
-        tie["dattn"] += (de_h.abs() * z.abs() * (1 - SLOPE) * near).sum((0, 1))
-        tie["dW_s"] += th.einsum("nuh,nuf->hf", jump, x.abs())
-        js = jump.sum(1)
-        tie["db_s"] += js.sum(0)
-        tie["db_d"] += js.sum(0)
-        tie["dW_d"] += js.T @ xv.abs()
-        del z, pos, de_h, near, jump
-        Sb = th.einsum("nuk,nuf->nkf", a, x).repeat_interleave(64, dim=1)
-        acc["dW_s"] += th.einsum("nuh,nuf->hf", dz, x) + th.einsum("nh,nhf->hf", g, Sb)
-        dzs = dz.sum(1)
-        del dz
-        acc["db_s"] += g.sum(0) + dzs.sum(0)
-        acc["db_d"] += dzs.sum(0)
-        acc["dW_d"] += dzs.T @ xv
-        acc["dW_r"] += g.T @ xv
-        acc["db_r"] += g.sum(0)
-    return [acc[nm] for nm in NAMES], [tie[nm] for nm in NAMES]
 
 
 def _vs_generic(g, g_gen):
