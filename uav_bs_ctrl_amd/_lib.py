@@ -20,6 +20,9 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "uavgnn.h")   # th
 # the second shared object: entry points that replace no reference call site (include/uavgnn_ext.h, csrc/ext/*.hip)
 EXT_LIB_PATH = os.environ.get("UAVGNN_EXT_LIB") or os.path.join(_HERE, "csrc", "libuavgnn_ext.so")
 EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "uavgnn_ext.h")
+# the third: the quantile-regression head and its TD tail (include/uavgnn_qr.h, csrc/qr/*.hip)
+QR_LIB_PATH = os.environ.get("UAVGNN_QR_LIB") or os.path.join(_HERE, "csrc", "libuavgnn_qr.so")
+QR_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "uavgnn_qr.h")
 
 
 class UavGnnError(RuntimeError):
@@ -83,9 +86,12 @@ SIGNATURES, _CONSTANTS = _read_header()
 globals().update(_CONSTANTS)
 # the same reading of include/uavgnn_ext.h; it defines no constant of its own (the error codes are the main library's)
 EXT_SIGNATURES = _read_header(EXT_HEADER_PATH)[0]
+# and of include/uavgnn_qr.h (no constant of its own either)
+QR_SIGNATURES = _read_header(QR_HEADER_PATH)[0]
 
 _LIB = None
 _EXT = None
+_QR = None
 
 
 def lib() -> ctypes.CDLL:
@@ -123,6 +129,21 @@ def ext() -> ctypes.CDLL:
             fn.restype, fn.argtypes = res, args
         _EXT = handle
     return _EXT
+
+
+def qr() -> ctypes.CDLL:
+    """Loads libuavgnn_qr.so once (``build.build_lib`` builds it beside the other two).  Fails loudly when it is missing."""
+    global _QR
+    if _QR is None:
+        if not os.path.exists(QR_LIB_PATH):
+            raise UavGnnError(f"{QR_LIB_PATH} is missing - build it with `python -c 'import __graft_entry__ as g; "
+                              f"g.build()'`.  uav_bs_ctrl_amd has no CPU / eager fallback.")
+        handle = ctypes.CDLL(QR_LIB_PATH)
+        for name, (res, args) in QR_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = res, args
+        _QR = handle
+    return _QR
 
 
 def check(code: int, what: str) -> None:

@@ -16,7 +16,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..graph import FlatObsBatch, HeteroBatch, RelationView
-from .heads import DuelingLayer, NoisyLinear, build_head
+from .heads import DuelingLayer, NoisyLinear, QuantileLinear, build_head
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -124,7 +124,8 @@ def _gru(cell: nn.GRUCell, i_parts, h):
 
 def _head(f_out, h):
     """Q head (gnn_agents.py:43-46,:56)."""
-    if isinstance(f_out, (DuelingLayer, NoisyLinear)):      # (a NoisyLinear in its mode "off" is the plain head on its means)
+    # (a NoisyLinear in its mode "off" is the plain head on its means; a QuantileLinear gives means or quantiles by its mode)
+    if isinstance(f_out, (DuelingLayer, NoisyLinear, QuantileLinear)):
         return f_out(h)
     return ops.linear(h, f_out.weight, f_out.bias)
 
@@ -406,7 +407,7 @@ class DrqnGnnAgent(nn.Module):
         d = self._hidden_size // self._n_heads
         self.enc = GATv2Conv((obs_shape["gt"], obs_shape["agent"]), d, self._n_heads)
         self.rnn = nn.GRUCell(self._hidden_size, self._hidden_size)
-        if getattr(args, "dueling", False) and getattr(args, "noisy", None) is None:
+        if getattr(args, "dueling", False) and getattr(args, "noisy", None) is None and getattr(args, "quantiles", None) is None:
             self.f_out = nn.Linear(self._hidden_size, n_actions)       # the DRQN agent has no dueling form (drqn/agents/gnn_agents.py:17)
         else:
             self.f_out = build_head(self._hidden_size, n_actions, args)

@@ -11,6 +11,12 @@ uses) each call site of the plain head computes the plain head on the means, lau
 network's heads for a scope: "rows" (training rollouts: one draw per row inside ONE launch of csrc/ext/noisy_head.hip, one step of the
 module's device pair ``rng_state`` consumed per call) or "shared" (an update: ONE draw folded into effective parameters at the start
 of the scope, ``ops.noisy_fold``, used by every step of that scope).
+
+``QuantileLinear`` is the distributional head in quantile-regression form (QR-DQN; include/uavgnn_qr.h): K quantile values per action
+under ``nn.Linear``'s parameter names, ``weight [A*K, H]`` / ``bias [A*K]``.  It is NOT an ``nn.Linear``: the fused TarMAC step keys on
+that type and has no form for a head this wide, so an agent with this head takes the generic route (communication block, then the
+head).  ``quantile_mode`` sets what a call returns for a scope: "mean" (the default: q [N, A], the mean over the quantiles - rollouts,
+``act``, evaluations, films) or "quantiles" (theta [N, A*K]: the two forward passes of an update).
 """
 import contextlib
 import math
@@ -146,8 +152,72 @@ def noisy_mode(net, mode):
             m.noisy_mode, m._fold = mode0, fold0
 
 
+class QuantileLinear(nn.Module):
+    """theta = h W^T + b with W [A*K, H], b [A*K]: theta[n, a*K + i] is the value of action a at the fraction tau_i = (2 i + 1) / (2 K);
+    Q(a) = mean_i theta[a, i].  Initialised like ``nn.Linear(in_feats, A*K)``.  Mode "mean" without autograd on the GPU: ONE
+    ``uavgnn_qr_mean_fold`` launch gives (W_bar, b_bar), then the plain head runs on them.  The fold is recomputed per call - the fused
+    optimizer writes parameters through raw pointers, so no version counter tells when they changed, and a call inside a captured graph
+    must replay with the parameters of the replay.  Under grad, on the CPU or in float64 "mean" is the torch expression."""
+
+    def __init__(self, in_feats, n_actions, K):
+        super().__init__()
+        if isinstance(K, bool) or not isinstance(K, int) or K not in ops.QR_K:
+            raise ValueError(f"quantiles: K must be one of {ops.QR_K}, got {K!r}")
+        if not 1 <= n_actions <= 64:
+            raise ValueError(f"quantiles: 1 <= n_actions <= 64 expected, got {n_actions}")
+        self.in_features, self.n_actions, self.K = in_feats, n_actions, K
+        lin = nn.Linear(in_feats, n_actions * K)
+        self.weight, self.bias = lin.weight, lin.bias
+        self.quantile_mode = "mean"
+
+    def extra_repr(self):
+        return f"in_features={self.in_features}, n_actions={self.n_actions}, K={self.K}"
+
+    def forward(self, x):
+        A, K = self.n_actions, self.K
+        if self.quantile_mode == "quantiles":
+            return ops.linear(x, self.weight, self.bias) if x.dim() == 2 else nn.functional.linear(x, self.weight, self.bias)
+        needs_grad = th.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad or self.bias.requires_grad)
+        if needs_grad or x.dim() != 2 or not (x.is_cuda and x.dtype == th.float32 and self.weight.is_cuda):
+            W_bar, b_bar = ops.quantile_mean_fold_torch(self.weight, self.bias, A, K)
+            return nn.functional.linear(x, W_bar, b_bar)
+        with th.no_grad():
+            W_bar, b_bar = ops.quantile_mean_fold(self.weight, self.bias, A, K)
+            return ops.head_fwd(x if x.is_contiguous() else x.contiguous(), W_bar, b_bar)
+
+
+def quantile_heads(net):
+    """The QuantileLinear modules of a network (a list; empty for every other head form)."""
+    return [m for m in net.modules() if isinstance(m, QuantileLinear)]
+
+
+@contextlib.contextmanager
+def quantile_mode(net, mode):
+    """Sets what the quantile heads of `net` (a module, or the list ``quantile_heads`` gave) return for the scope: "mean" or
+    "quantiles"; the previous mode returns on exit."""
+    if mode not in ("mean", "quantiles"):
+        raise ValueError(f"quantile_mode: unknown mode {mode!r} (mean, quantiles)")
+    heads = net if isinstance(net, (list, tuple)) else quantile_heads(net)
+    prev = [m.quantile_mode for m in heads]
+    for m in heads:
+        m.quantile_mode = mode
+    try:
+        yield heads
+    finally:
+        for m, mode0 in zip(heads, prev):
+            m.quantile_mode = mode0
+
+
 def build_head(in_feats, n_actions, args):
-    """The Q head an agent's `args` ask for: DuelingLayer (``dueling``), NoisyLinear (``noisy`` = sigma0, a number) or nn.Linear."""
+    """The Q head an agent's `args` ask for: DuelingLayer (``dueling``), NoisyLinear (``noisy`` = sigma0, a number), QuantileLinear
+    (``quantiles`` = K, an int) or nn.Linear."""
+    K = getattr(args, "quantiles", None)
+    if K is not None and not isinstance(K, bool) and isinstance(K, int):
+        if getattr(args, "dueling", False):
+            raise ValueError("quantiles together with dueling is not supported: the dueling quantile head does not exist; set one of the two")
+        if getattr(args, "noisy", None) is not None:
+            raise ValueError("quantiles together with noisy is not supported: the noisy quantile head does not exist; set one of the two")
+        return QuantileLinear(in_feats, n_actions, K)
     sigma0 = getattr(args, "noisy", None)
     if sigma0 is not None and not isinstance(sigma0, bool) and isinstance(sigma0, (int, float)):
         if getattr(args, "dueling", False):

@@ -1,10 +1,12 @@
-"""Builds ``libuavgnn.so`` (the C-ABI of include/uavgnn.h) and ``libuavgnn_ext.so`` (include/uavgnn_ext.h: the entry points that replace
-no reference call site, ``csrc/ext/*.hip``) for gfx950 with hipcc.  No GPU is needed to compile.
+"""Builds ``libuavgnn.so`` (the C-ABI of include/uavgnn.h), ``libuavgnn_ext.so`` (include/uavgnn_ext.h: the entry points that replace
+no reference call site, ``csrc/ext/*.hip``) and ``libuavgnn_qr.so`` (include/uavgnn_qr.h: the quantile-regression head and its TD tail,
+``csrc/qr/*.hip``) for gfx950 with hipcc.  No GPU is needed to compile.
 
     python -m uav_bs_ctrl_amd.build [--force]
 
 Every ``csrc/*.hip`` is compiled to its own object (in parallel, ``csrc/build/*.o``) and the objects are linked into the
-shared library (the objects of ``csrc/ext/*.hip``, ``csrc/build/ext/*.o``, into the second one, under the same rules and flags);
+shared library (the objects of ``csrc/ext/*.hip``, ``csrc/build/ext/*.o``, into the second one and those of ``csrc/qr/*.hip``,
+``csrc/build/qr/*.o``, into the third, under the same rules and flags);
 without ``--force`` only the objects older than their source (or than any header) are recompiled.
 ``__graft_entry__.build()`` always forces a full compile so that "it builds" is checked against the sources on disk
 and never against a shipped binary.
@@ -25,6 +27,9 @@ OUT = os.path.join(CSRC, "libuavgnn.so")
 EXT_CSRC = os.path.join(CSRC, "ext")
 EXT_OBJ = os.path.join(OBJ, "ext")
 EXT_OUT = os.path.join(CSRC, "libuavgnn_ext.so")
+QR_CSRC = os.path.join(CSRC, "qr")
+QR_OBJ = os.path.join(OBJ, "qr")
+QR_OUT = os.path.join(CSRC, "libuavgnn_qr.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # per-source flags: kernels that mix 16-bit-operand MFMAs with fp32 VALU work the compiler would pack (see the source's header).
@@ -48,7 +53,9 @@ EXTRA_CFLAGS = {"gatv2_bwd_mfma.hip": _NO_PK,
                 "td_return.hip": _NO_PK + ["-ffp-contract=off"],
                 # ext: VALU-heavy fp32 (Philox, Box-Muller) that may share a SIMD with the 16-bit MFMA kernels; the header fixes the order
                 # of single-rounded operations of the epilogue and of the fold
-                "noisy_head.hip": _NO_PK + ["-ffp-contract=off"]}
+                "noisy_head.hip": _NO_PK + ["-ffp-contract=off"],
+                # qr: the pairwise quantile loss is VALU-bound fp32 with fixed orders of single-rounded operations (include/uavgnn_qr.h)
+                "quantile.hip": _NO_PK + ["-ffp-contract=off"]}
 # Round 5: the fp32 backward kernels (csrc/gatv2.hip) and K5 (csrc/disc_comm.hip) held 8-40 operand-selected packed fp32
 # instructions each - safe only while no matrix-core kernel shares a SIMD with them (ANOTHER wavefront's 128-bit-operand MFMA
 # triggers the hazard too), i.e. under a one-stream calling convention.  Compiled without packed fp32 the pattern cannot occur at
@@ -114,8 +121,9 @@ def _build_one(csrc: str, obj_dir: str, out: str, force: bool, verbose: bool) ->
 
 
 def build_lib(force: bool = False, verbose: bool = True) -> str:
-    """Builds both shared objects; returns the path of the main one."""
+    """Builds the three shared objects; returns the path of the main one."""
     _build_one(EXT_CSRC, EXT_OBJ, EXT_OUT, force, verbose)
+    _build_one(QR_CSRC, QR_OBJ, QR_OUT, force, verbose)
     return _build_one(CSRC, OBJ, OUT, force, verbose)
 
 
@@ -123,3 +131,4 @@ if __name__ == "__main__":
     build_lib(force="--force" in sys.argv)
     print(OUT)
     print(EXT_OUT)
+    print(QR_OUT)

@@ -28,7 +28,7 @@ import torch.nn.functional as F
 from . import _lib as L
 from . import ops
 from .agents import REGISTRY as agent_REGISTRY
-from .agents.heads import noisy_heads, noisy_mode
+from .agents.heads import noisy_heads, noisy_mode, quantile_heads, quantile_mode
 
 
 class FlatGradBuffer:
@@ -93,9 +93,29 @@ class MultiAgentQLearner:
     (``ops.td_return_loss``; DESIGN "Multi-step TD targets").
     noisy: None (the plain / dueling head; every launch as it was) or sigma0, a number: the noisy-net Q head (agents/heads.py
     ``NoisyLinear``; DESIGN "Noisy-net exploration") - ``act`` and the rollout steps of ``graphs`` draw per row (``rollout_noise``),
-    ``loss`` folds one draw per network, evaluations use the means.  The caller's ``args`` object is left as it is."""
+    ``loss`` folds one draw per network, evaluations use the means.
+    quantiles: None (every launch as it was) or K in {8, 16, 32, 64}: the distributional value function in quantile-regression form
+    (agents/heads.py ``QuantileLinear``; DESIGN "Distributional Q: quantile regression") - the head gives K quantiles per action, ``act``
+    and every evaluation use their means, ``loss`` is the quantile-Huber loss at kappa = 1 on one-step or ``("nstep", n)`` targets
+    (``ops.qr_select`` / ``ops.qr_loss``).  Lambda returns and the QMIX mixer have no quantile form and are refused.
+    The caller's ``args`` object is left as it is."""
 
-    def __init__(self, env_info: dict, args, process_group=None, returns=None, noisy=None):
+    QR_KAPPA = 1.0
+
+    def __init__(self, env_info: dict, args, process_group=None, returns=None, noisy=None, quantiles=None):
+        if quantiles is None:
+            quantiles = getattr(args, "quantiles", None)      # `series` rebuilds the head of a run directory through `args`
+        if quantiles is not None:
+            if isinstance(quantiles, bool) or not isinstance(quantiles, int) or quantiles not in ops.QR_K:
+                raise ValueError(f"quantiles: None or K in {ops.QR_K} expected, got {quantiles!r}")
+            if ops.normalize_returns(returns) is not None and ops.normalize_returns(returns)[0] == "lambda":
+                raise ValueError("quantiles together with returns=('lambda', lam) is not supported: the quantile form of lambda returns "
+                                 "does not exist; use ('nstep', n)")
+            if getattr(args, "mixer", False):
+                raise ValueError("quantiles together with mixer=True is not supported: the quantile form of the QMIX mixer does not exist")
+            args = copy.copy(args)
+            args.quantiles = int(quantiles)
+        self.quantiles = quantiles
         if noisy is not None:
             if isinstance(noisy, bool) or not isinstance(noisy, (int, float)):
                 raise ValueError(f"noisy: sigma0 must be a number, got {noisy!r}")
@@ -119,6 +139,7 @@ class MultiAgentQLearner:
             p.requires_grad_(False)
         self.params = list(self.policy_net.parameters())
         self._noisy_policy, self._noisy_target = noisy_heads(self.policy_net), noisy_heads(self.target_net)
+        self._quantile_heads = quantile_heads(self.policy_net) + quantile_heads(self.target_net)
         self.mixer = None
         if getattr(args, "mixer", False):   # QMIX (learner.py:35-40); every launcher of the reference sets mixer=False
             from copy import deepcopy
@@ -264,7 +285,12 @@ class MultiAgentQLearner:
         h0 / h1 [B*n, H] (stored hidden states of the first two steps), acts [T, B*n, 1] int64,
         rews [T, B, n or 1], dones [T, B, 1]; optional obs_all = the T+1 observation graphs batched in time-major
         order (``graph.batch(obs)``), which switches on the time-batched encoder.
-        With the noisy head each network folds ONE draw at its own pair here and uses it for all its steps of this call."""
+        With the noisy head each network folds ONE draw at its own pair here and uses it for all its steps of this call.
+        With the quantile head both networks return their quantiles here, and the second result is the policy's per-action MEANS
+        q_pol [T+1, N, n_actions] (what ``accumulate`` reports as QVals), the third the target's quantiles [T, N, n_actions * K]."""
+        if self._quantile_heads:
+            with quantile_mode(self._quantile_heads, "quantiles"):
+                return self._loss(batch)
         if not self._noisy_policy:
             return self._loss(batch)
         with noisy_mode(self._noisy_policy, "shared"), noisy_mode(self._noisy_target, "shared"):
@@ -324,6 +350,8 @@ class MultiAgentQLearner:
 
     def _td_loss(self, batch: Dict, T: int, agent_out: th.Tensor, target_out: th.Tensor) -> tuple:
         """learner.py:134-154 on the stacked Q values agent_out [T+1, N, n_actions] / target_out [T, N, n_actions]."""
+        if getattr(self, "quantiles", None) is not None:      # (callers hand this method a bare namespace of the one-step tail's fields)
+            return self._td_loss_quantile(batch, T, agent_out, target_out)
         if self.returns is not None:
             return self._td_loss_returns(batch, T, agent_out, target_out)
         qvals = agent_out[:-1].gather(2, batch["acts"])
@@ -381,6 +409,29 @@ class MultiAgentQLearner:
             else:
                 chunks.append(td)
         return loss, agent_out, target_out
+
+    def _td_loss_quantile(self, batch: Dict, T: int, agent_out: th.Tensor, target_out: th.Tensor) -> tuple:
+        """``_td_loss`` with ``quantiles`` set, on the stacked quantiles agent_out [T+1, N, A*K] / target_out [T, N, A*K]: select on the
+        quantile means -> quantile-Huber loss on one-step or n-step targets (``ops.qr_select`` / ``ops.qr_loss``: csrc/qr/quantile.hip
+        on the GPU).  Same contract for ``weights``, ``td_out``, ``last_td`` and ``_td_chunks`` as ``_td_loss_returns``; the TD error of
+        a row is the difference of the quantile means.  No host sync; the loss's partial sums live in ``_td_workspace``."""
+        A, K = self.n_actions, self.quantiles
+        N = agent_out.shape[1]
+        theta_a, theta_next, _, q_pol = ops.qr_select(agent_out.view(T + 1, N, A, K), target_out.view(T, N, A, K), batch["acts"],
+                                                      self.double_q)
+        B = batch["rews"].shape[1]
+        weights = batch.get("weights")
+        n_step = 1 if self.returns is None else self.returns[1]
+        loss, td = ops.qr_loss(theta_a.view(T, B, self.n_agents, K), theta_next.view(T, B, self.n_agents, K), batch["rews"], batch["dones"],
+                               weights, self.gamma, n_step, self.QR_KAPPA,
+                               td_out=batch.get("td_out") if weights is not None else None, workspace=self._td_workspace)
+        if weights is not None:
+            chunks = getattr(self, "_td_chunks", None)
+            if chunks is None:
+                self.last_td = [td]
+            else:
+                chunks.append(td)
+        return loss, q_pol, target_out
 
     def update(self, batch) -> Dict:
         """One gradient step = ``accumulate`` (loss + backward into the flat gradient buffer) -> the ONE collective of the
@@ -516,16 +567,17 @@ class QLearner(MultiAgentQLearner):
     env_info: the wrapper's dict (``BatchedSingleUbsCoverageEnv.get_env_info``: obs_shape, n_actions, episode_limit).  args: the
     reference's DRQN config (algos/drqn/config.py); ``dueling`` defaults to False when it is missing (the DRQN config has no
     such switch), ``double_q`` and ``mixer`` are not read.  The caller's ``args`` object is left as it is.  returns: passed through to
-    the parent (multi-step targets on ``max`` bootstrap values, C = 1)."""
+    the parent (multi-step targets on ``max`` bootstrap values, C = 1).  quantiles: passed through as well (the target's quantiles at the
+    action of the largest quantile mean)."""
 
-    def __init__(self, env_info: dict, args, process_group=None, returns=None, noisy=None):
+    def __init__(self, env_info: dict, args, process_group=None, returns=None, noisy=None, quantiles=None):
         args = copy.copy(args)
         if not hasattr(args, "dueling"):
             args.dueling = False
         args.double_q, args.mixer = False, False
         info = dict(env_info)
         info["n_agents"] = 1
-        super().__init__(info, args, process_group, returns, noisy)
+        super().__init__(info, args, process_group, returns, noisy, quantiles)
 
     def _build_agent(self):
         """learner.py:48-52: an integer observation size -> 'rnn' (flattened observations), a dict of feature sizes -> the

@@ -1259,7 +1259,190 @@ def td_return_loss(qvals, next_vals, rews, dones, weights, gamma, returns, td_ou
     return x.sum() / max(d.numel(), 1), td
 
 
-RELU_BWD_FUSED = os.environ.get("UAVGNN_RELU_BWD_FUSED", "1") != "0"   # ReLU mask + bias gradient in one pass (A/B switch)
+# ---------------------------------------------------------------------------------------------------------------------
+# Distributional Q, quantile-regression form (include/uavgnn_qr.h, csrc/qr/quantile.hip; DESIGN "Distributional Q")
+# ---------------------------------------------------------------------------------------------------------------------
+QR_K = (8, 16, 32, 64)     # the quantile counts of uavgnn_qr_supported (1 <= A <= 64)
+
+
+def _qr_device(*tensors) -> bool:
+    """The kernels take CUDA float32; CPU and float64 tensors take the torch arms."""
+    return all(t.is_cuda and t.dtype == th.float32 for t in tensors)
+
+
+def quantile_mean_fold_torch(weight, bias, A, K):
+    H = weight.shape[1]
+    return weight.view(A, K, H).sum(1) * (1.0 / K), bias.view(A, K).sum(1) * (1.0 / K)
+
+
+def quantile_mean_fold(weight, bias, A, K):
+    """(W_bar [A, H], b_bar [A]) of a quantile head's weight [A*K, H] / bias [A*K]: the mean over the K quantiles of every action, so
+    that q = h W_bar^T + b_bar is the mean of theta = h W^T + b.  ONE launch on the GPU, no autograd (``QuantileLinear`` uses it where
+    no gradient is asked for); CPU / float64 tensors, or a call under grad, take ``quantile_mean_fold_torch``."""
+    if tuple(weight.shape[:1]) != (A * K,) or tuple(bias.shape) != (A * K,):
+        raise L.UavGnnError(f"quantile_mean_fold: weight {tuple(weight.shape)} / bias {tuple(bias.shape)} do not fit [A*K = {A * K}, H] / [A*K]")
+    needs_grad = th.is_grad_enabled() and (weight.requires_grad or bias.requires_grad)
+    if needs_grad or not _qr_device(weight, bias):
+        return quantile_mean_fold_torch(weight, bias, A, K)
+    H = weight.shape[1]
+    weight = weight.detach()
+    weight = weight if weight.stride(1) == 1 else weight.contiguous()
+    bias = bias.detach().contiguous()
+    W_bar = th.empty((A, H), dtype=th.float32, device=weight.device)
+    b_bar = th.empty((A,), dtype=th.float32, device=weight.device)
+    with KERNEL_TIMER.span("qr_mean_fold", (A, K, H)):
+        rc = L.qr().uavgnn_qr_mean_fold(weight.data_ptr(), weight.stride(0), bias.data_ptr(), A, K, H, W_bar.data_ptr(), b_bar.data_ptr(),
+                                        L.stream())
+    L.check(rc, "uavgnn_qr_mean_fold")
+    return W_bar, b_bar
+
+
+def qr_select_torch(theta_pol, theta_tgt, acts, double_q):
+    """The select of the quantile TD tail in torch ops (differentiable towards theta_pol through theta_a only):
+    theta_pol [T+1, N, A, K], theta_tgt [T, N, A, K], acts [T, N] (or [T, N, 1]) int64 ->
+    (theta_a [T, N, K], theta_next [T, N, K], next_acts [T, N] int64, q_pol [T+1, N, A])."""
+    T, N, A, K = theta_tgt.shape
+    idx = acts.reshape(T, N, 1, 1).expand(T, N, 1, K)
+    theta_a = theta_pol[:-1].gather(2, idx).view(T, N, K)
+    q_pol = theta_pol.detach().sum(-1) * (1.0 / K)
+    pick = theta_pol[1:].detach().sum(-1) if double_q else theta_tgt.detach().sum(-1)
+    next_acts = pick.argmax(2)
+    theta_next = theta_tgt.detach().gather(2, next_acts.view(T, N, 1, 1).expand(T, N, 1, K)).view(T, N, K)
+    return theta_a, theta_next, next_acts, q_pol
+
+
+class _QrSelect(th.autograd.Function):
+    """The select on quantile rows in one pass (csrc/qr/quantile.hip); the backward writes all of d_theta_pol."""
+
+    @staticmethod
+    def forward(ctx, theta_pol, theta_tgt, acts, double_q):
+        L.require_gpu(theta_pol, theta_tgt, acts)
+        theta_pol, theta_tgt = L.f32c(theta_pol), L.f32c(theta_tgt)
+        T1, N, A, K = theta_pol.shape
+        T = T1 - 1
+        if tuple(theta_tgt.shape) != (T, N, A, K) or acts.dtype != th.int64 or acts.numel() != T * N:
+            raise L.UavGnnError(f"qr_select: theta_pol {tuple(theta_pol.shape)}, theta_tgt {tuple(theta_tgt.shape)}, acts "
+                                f"{tuple(acts.shape)} {acts.dtype} do not fit [T+1, N, A, K] / [T, N, A, K] / [T, N] int64")
+        acts = acts if acts.is_contiguous() else acts.contiguous()
+        dev = theta_pol.device
+        theta_a = th.empty((T, N, K), dtype=th.float32, device=dev)
+        theta_next = th.empty_like(theta_a)
+        next_acts = th.empty((T, N), dtype=th.int32, device=dev)
+        q_pol = th.empty((T1, N, A), dtype=th.float32, device=dev)
+        with KERNEL_TIMER.span("qr_select_fwd", (T, N, A, K)):
+            rc = L.qr().uavgnn_qr_select_fwd(theta_pol.data_ptr(), theta_tgt.data_ptr(), acts.data_ptr(), T, N, A, K, int(bool(double_q)),
+                                             theta_a.data_ptr(), theta_next.data_ptr(), next_acts.data_ptr(), q_pol.data_ptr(), L.stream())
+        L.check(rc, "uavgnn_qr_select_fwd")
+        ctx.save_for_backward(acts)
+        ctx.dims = (T, N, A, K)
+        ctx.mark_non_differentiable(theta_next, next_acts, q_pol)
+        return theta_a, theta_next, next_acts, q_pol
+
+    @staticmethod
+    def backward(ctx, d_theta_a, _d_next, _d_acts, _d_q):
+        acts, = ctx.saved_tensors
+        T, N, A, K = ctx.dims
+        d_theta_a = L.f32c(d_theta_a)
+        d_theta_pol = th.empty((T + 1, N, A, K), dtype=th.float32, device=d_theta_a.device)
+        with KERNEL_TIMER.span("qr_select_bwd", (T, N, A, K)):
+            rc = L.qr().uavgnn_qr_select_bwd(d_theta_a.data_ptr(), acts.data_ptr(), T, N, A, K, d_theta_pol.data_ptr(), L.stream())
+        L.check(rc, "uavgnn_qr_select_bwd")
+        return d_theta_pol, None, None, None
+
+
+def qr_select(theta_pol, theta_tgt, acts, double_q):
+    """theta_pol [T+1, N, A, K], theta_tgt [T, N, A, K], acts [T, N] or [T, N, 1] int64 -> (theta_a [T, N, K], theta_next [T, N, K],
+    next_acts [T, N], q_pol [T+1, N, A]): the quantiles of Q(s_t, a_t), those of the target network at the action whose quantile MEAN is
+    largest - on theta_pol[t+1] (``double_q``) or on theta_tgt[t] itself -, that action (int32 on the GPU) and the policy's per-action
+    means.  Only theta_a carries a gradient.  CUDA float32 tensors run csrc/qr/quantile.hip, all others ``qr_select_torch``."""
+    if _qr_device(theta_pol, theta_tgt):
+        return _QrSelect.apply(theta_pol, theta_tgt, acts, double_q)
+    return qr_select_torch(theta_pol, theta_tgt, acts, double_q)
+
+
+def qr_loss_torch(theta_a, theta_next, rews, dones, weights, gamma, n_step=1, kappa=1.0):
+    """(loss, td) of the quantile-Huber loss (QR-DQN eq. 10; include/uavgnn_qr.h) in torch ops, differentiable towards theta_a:
+    theta_a, theta_next [T, B, C, K]; rews [T, B, C] or [T, B, 1]; dones [T, B, 1]; weights [B] or None.  The n-step targets are
+    ``td_targets_torch`` per quantile; they carry no gradient.  Materialises [T, B, C, K, K]."""
+    T, B, C, K = theta_a.shape
+    y = td_targets_torch(theta_next.detach(), rews.reshape(T, B, -1, 1), dones.reshape(T, B, 1, 1), gamma, ("nstep", int(n_step)))
+    tau = (2 * th.arange(K, device=theta_a.device, dtype=theta_a.dtype) + 1) / (2 * K)
+    u = y.unsqueeze(-2) - theta_a.unsqueeze(-1)                       # [T, B, C, i, j]
+    au = u.abs()
+    huber = th.where(au <= kappa, 0.5 * u * u, kappa * (au - 0.5 * kappa))
+    wt = (tau.view(K, 1) - (u.detach() < 0).to(u.dtype)).abs()
+    rows = (wt * huber).sum(-1).sum(-1) * (1.0 / K) / kappa          # [T, B, C]
+    if weights is not None:
+        rows = rows * weights.view(1, B, 1)
+    td = (theta_a.detach().mean(-1) - y.mean(-1))
+    return rows.sum() / (T * B * C), td
+
+
+class _QrLoss(th.autograd.Function):
+    """Targets, the K x K pairs, loss, td and g = d loss / d theta_a in one call (csrc/qr/quantile.hip); the backward is g * grad_output."""
+
+    @staticmethod
+    def forward(ctx, theta_a, theta_next, rews, dones, weights, gamma, n_step, kappa, td, workspace):
+        L.require_gpu(theta_a, theta_next, rews, dones, weights, td)
+        theta_a, theta_next, rews, dones = L.f32c(theta_a), L.f32c(theta_next), L.f32c(rews), L.f32c(dones)
+        T, B, C, K = theta_a.shape
+        Cr = rews.shape[-1]
+        if tuple(theta_next.shape) != (T, B, C, K) or tuple(rews.shape) != (T, B, Cr) or dones.numel() != T * B:
+            raise L.UavGnnError(f"qr_loss: theta_a {tuple(theta_a.shape)}, theta_next {tuple(theta_next.shape)}, rews {tuple(rews.shape)}, "
+                                f"dones {tuple(dones.shape)} do not fit [T, B, C, K] / [T, B, C, K] / [T, B, 1 or C] / [T, B, 1]")
+        if weights is not None:
+            weights = L.f32c(weights)
+            if weights.numel() != B:
+                raise L.UavGnnError(f"qr_loss: {weights.numel()} weights for {B} sequences")
+        dev = theta_a.device
+        if tuple(td.shape) != (T, B, C) or td.dtype != th.float32 or not td.is_contiguous():
+            raise L.UavGnnError(f"qr_loss: td_out must be a contiguous float32 [{T}, {B}, {C}], got {tuple(td.shape)} {td.dtype}")
+        lib = L.qr()
+        G = lib.uavgnn_qr_loss_partials(T, B, C, K)
+        if G < 1:
+            L.check(G, "uavgnn_qr_loss_partials")
+        if workspace is None:
+            partials = th.empty(G, dtype=th.float32, device=dev)
+        else:       # the caller's store (the learner's): one buffer per shape, handed to every call
+            partials = workspace.get(("qr", G, dev))
+            if partials is None:
+                partials = workspace[("qr", G, dev)] = th.empty(G, dtype=th.float32, device=dev)
+        g = th.empty((T, B, C, K), dtype=th.float32, device=dev)
+        loss = th.empty((), dtype=th.float32, device=dev)
+        with KERNEL_TIMER.span("qr_loss_fwd", (T, B, C, K)):
+            rc = lib.uavgnn_qr_loss_fwd(theta_a.data_ptr(), theta_next.data_ptr(), rews.data_ptr(), Cr, dones.data_ptr(), L.ptr(weights), T, B,
+                                        C, K, float(gamma), int(n_step), float(kappa), td.data_ptr(), g.data_ptr(), loss.data_ptr(),
+                                        partials.data_ptr(), G, L.stream())
+        L.check(rc, "uavgnn_qr_loss_fwd")
+        ctx.save_for_backward(g)
+        return loss
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        g, = ctx.saved_tensors
+        return g * d_loss, None, None, None, None, None, None, None, None, None
+
+
+def qr_loss(theta_a, theta_next, rews, dones, weights, gamma, n_step=1, kappa=1.0, td_out=None, workspace=None):
+    """(loss, td) of the quantile-regression TD loss: theta_a, theta_next [T, B, C, K] (``qr_select``'s, viewed per environment); rews
+    [T, B, C] or [T, B, 1]; dones [T, B, 1]; weights [B] or None (= 1); n-step targets per quantile (n_step = 1: the one-step target).
+    loss = sum_b w_b l / (T B C) with l the quantile-Huber row loss at threshold kappa; its gradient reaches theta_a only.  td [T, B, C] =
+    mean_i theta_i - mean_j y_j (no gradient; written straight into ``td_out`` when one is given).  workspace: a dict that keeps the
+    per-workgroup partial sums between calls.  CUDA float32 tensors run csrc/qr/quantile.hip, all others ``qr_loss_torch``."""
+    if isinstance(n_step, bool) or int(n_step) != n_step or n_step < 1:
+        raise ValueError(f"qr_loss: n_step must be an integer >= 1, got {n_step!r}")
+    if not kappa > 0:
+        raise ValueError(f"qr_loss: kappa must be positive, got {kappa!r}")
+    if _qr_device(theta_a, theta_next):
+        td = td_out if td_out is not None else th.empty(tuple(theta_a.shape[:3]), dtype=th.float32, device=theta_a.device)
+        return _QrLoss.apply(theta_a, theta_next, rews, dones, weights, gamma, int(n_step), float(kappa), td, workspace), td
+    loss, td = qr_loss_torch(theta_a, theta_next, rews, dones, weights, gamma, n_step, kappa)
+    if td_out is not None:
+        td = td_out.copy_(td)
+    return loss, td
+
+
+RELU_BWD_FUSED =os.environ.get("UAVGNN_RELU_BWD_FUSED", "1") != "0"   # ReLU mask + bias gradient in one pass (A/B switch)
 
 
 class _LinearReLU(th.autograd.Function):

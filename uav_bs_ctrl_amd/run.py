@@ -5,7 +5,8 @@ log rows, checkpoints, trajectory films and resume.
     run.train()                          # all remaining epochs; run.train(epochs=k): k more
     run = Run.resume("data/exp3_8ubs_s0")    # rebuilds everything from config.json + state.pt and goes on, bit for bit
     python -m uav_bs_ctrl_amd.run --exp exp3 --env 8ubs --args-json args.json --out data/exp3_8ubs_s0 [--seed 0 --envs 32 --resume --eager --compact-replay
-                                  --prioritized ALPHA BETA ETA EPS --returns nstep 3 | --returns lambda 0.8 --noisy SIGMA0]
+                                  --prioritized ALPHA BETA ETA EPS --returns nstep 3 | --returns lambda 0.8 --noisy SIGMA0
+                                  --quantiles K]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N -m uav_bs_ctrl_amd.run ...     # data-parallel: N ranks, one GPU each
 
 This is host orchestration over launches that exist: a collect-only and a training ``graphs.GraphedEpisode``, one
@@ -306,13 +307,14 @@ def _reference_env(exp: str, env) -> tuple:
 
 def run_config(exp: str, env, ns, seed: int = 0, n_envs: int = 32, n_test_envs: Optional[int] = None, updates_per_segment: int = 1,
                graphed: bool = True, save_replay: bool = True, world: int = 1, force_collective: bool = False,
-               compact_replay: bool = False, prioritized=None, returns=None, noisy=None) -> dict:
+               compact_replay: bool = False, prioritized=None, returns=None, noisy=None, quantiles=None) -> dict:
     """The ``uav_bs_ctrl_amd`` entry of ``config.json``: everything of ``Run.create``'s arguments that ``Run.resume`` needs to rebuild the
     same run (host only).  compact_replay with exp1 is a ``ValueError``: the single-UBS observations are M x 4 floats already.
     prioritized: None, or (alpha, beta, eta, eps) - the key ``prioritized`` enters the entry ONLY when set (absent means off, so a
     directory written before the option existed resumes unchanged).  returns: None, ("nstep", n) or ("lambda", lam) - the learner's
     multi-step TD target; the key ``returns`` likewise enters ONLY when set.  noisy: None or sigma0, a number - the noisy-net Q head;
-    the key ``noisy`` likewise enters ONLY when set."""
+    the key ``noisy`` likewise enters ONLY when set.  quantiles: None or K, the number of quantiles of the distributional Q head; the key
+    ``quantiles`` likewise enters ONLY when set."""
     if compact_replay and exp == "exp1":
         raise ValueError("compact_replay: the compact ring stores the multi-UBS simulator's state (exp2 / exp3); exp1's observations "
                          "are already n_gts x 4 floats per step")
@@ -326,7 +328,16 @@ def run_config(exp: str, env, ns, seed: int = 0, n_envs: int = 32, n_test_envs: 
         out["returns"] = _returns(returns)
     if noisy is not None:
         out["noisy"] = _noisy(noisy)
+    if quantiles is not None:
+        out["quantiles"] = _quantiles(quantiles)
     return out
+
+
+def _quantiles(value) -> int:
+    """K of the quantile-regression Q head as config.json holds it: one of the kernel's quantile counts (8, 16, 32, 64)."""
+    if isinstance(value, bool) or not isinstance(value, int) or value not in (8, 16, 32, 64):
+        raise ValueError(f"quantiles: None or K in (8, 16, 32, 64) expected, got {value!r}")
+    return int(value)
 
 
 def _noisy(value) -> float:
@@ -411,6 +422,8 @@ class Run:
         self.returns = tuple(_returns(ours["returns"])) if ours.get("returns") is not None else None
         # absent likewise: the plain / dueling head, the reference's exploration alone
         self.noisy = _noisy(ours["noisy"]) if ours.get("noisy") is not None else None
+        # absent likewise: a scalar Q value per action
+        self.quantiles = _quantiles(ours["quantiles"]) if ours.get("quantiles") is not None else None
         if getattr(args, "mixer", False):
             raise ValueError("mixer = True is not covered by the driver yet: graphs.Episode / GraphedEpisode train with a mixer, "
                              "Run does not build one")
@@ -429,8 +442,9 @@ class Run:
         self.enc, self.env, self.test_env = enc, make(E, "train_env"), make(E_test, "test_env") if self.rank == 0 else None
         env, test_env = self.env, self.test_env
         th.manual_seed(seeds["torch"])           # parameter initialisation (data-parallel: rank 0's are broadcast)
+        opts = dict(quantiles=self.quantiles) if self.quantiles is not None else {}
         self.learner = learner = (QLearner if self.single else MultiAgentQLearner)(env.get_env_info(enc), args, process_group=self.group,
-                                                                                   returns=self.returns, noisy=self.noisy)
+                                                                                   returns=self.returns, noisy=self.noisy, **opts)
         if force:
             learner.grads.force_collective = True        # before anything is captured: the episode graphs are cut at the all-reduce
         assert learner.needs_collective() == self.collective
@@ -473,7 +487,7 @@ class Run:
     def create(cls, exp: str, env, args, output_dir: str, exp_name: Optional[str] = None, seed: int = 0, n_envs: int = 32,
                n_test_envs: Optional[int] = None, updates_per_segment: int = 1, graphed: bool = True, save_replay: bool = True,
                group=None, force_collective: bool = False, compact_replay: bool = False, prioritized=None, returns=None,
-               noisy=None) -> "Run":
+               noisy=None, quantiles=None) -> "Run":
         """Builds simulators, learner, replay, statistics, film and the three graphs (``graphed=False``: their eager forms) as
         run.py:47-61 builds them and writes ``config.json``; sets torch's generator (``torch.manual_seed(seed)``, as the reference's
         ``set_rand_seed`` does) for the parameter initialisation.  env: a map id of ``sim.MAPS`` or a ``MapSpec`` (exp2 / exp3), a
@@ -490,6 +504,10 @@ class Run:
         noisy=sigma0: the noisy-net Q head (``MultiAgentQLearner(noisy=...)``) - per-row draws in the rollouts, one folded draw per
         network and update, the means in evaluations; the sigmas travel in the state_dict, both networks' noise pairs in ``state.pt``
         (``comm.*``) and the policy's in checkpoints (``comm_rng_state``).  The epsilon schedule is untouched.  None: not one launch differs.
+        quantiles=K (8, 16, 32 or 64): the distributional value function in quantile-regression form
+        (``MultiAgentQLearner(quantiles=...)``) - ``f_out.weight`` is [n_actions * K, H] in checkpoints, rollouts and evaluations act on the
+        quantile means, the update is the quantile-Huber loss on one-step or ``("nstep", n)`` targets; with ``("lambda", lam)``, ``noisy``
+        or a dueling head: ``ValueError``.  It adds no collective and no random stream.  None: not one launch differs.
 
         With ``torch.distributed`` initialised the run is data-parallel over ``group`` (default: the world) and EVERY rank calls
         ``create`` with the same arguments but its own ``args.device``; ``n_envs`` and ``args.batch_size`` are per rank.
@@ -498,7 +516,7 @@ class Run:
         ns = check_args(exp, args)
         world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         ours = run_config(exp, env, ns, seed, n_envs, n_test_envs, updates_per_segment, graphed, save_replay, world, force_collective,
-                          compact_replay, prioritized, returns, noisy)
+                          compact_replay, prioritized, returns, noisy, quantiles)
         run = cls(ours, ns, output_dir, exp_name, resuming=False, group=group)
         if run.rank == 0:
             env_fn, env_kwargs = _reference_env(exp, env)
@@ -739,6 +757,9 @@ def _parser():
     ap.add_argument("--noisy", type=float, default=None, metavar="SIGMA0",
                     help="noisy-net Q head (factorised Gaussian, sigma = SIGMA0 / sqrt(hidden_size)): per-row draws in the rollouts, one "
                          "draw per network and update, the means in evaluations (no default: a number)")
+    ap.add_argument("--quantiles", type=int, default=None, metavar="K", choices=(8, 16, 32, 64),
+                    help="distributional Q head in quantile-regression form (QR-DQN): K quantiles per action, the quantile-Huber loss on "
+                         "one-step or '--returns nstep N' targets; not with --noisy, a dueling head or '--returns lambda'")
     ap.add_argument("--epochs", type=int, default=None, help="run this many more epochs, not all remaining ones")
     ap.add_argument("--dist-backend", choices=("nccl", "gloo"), default="nccl", help="under a launcher that sets RANK: the backend of the group")
     ap.add_argument("--dist-timeout", type=float, default=600.0, help="seconds after which a collective gives up on a missing rank")
@@ -767,7 +788,7 @@ def main(argv=None) -> None:
             run = Run.create(a.exp, _parse_env(a.exp, a.env), args, a.out, exp_name=a.exp_name or a.exp, seed=a.seed, n_envs=a.envs,
                              n_test_envs=a.test_envs, updates_per_segment=a.updates_per_segment, graphed=not a.eager,
                              save_replay=not a.no_save_replay, compact_replay=a.compact_replay, prioritized=a.prioritized,
-                             returns=returns, noisy=a.noisy)
+                             returns=returns, noisy=a.noisy, quantiles=a.quantiles)
         run.train(a.epochs)
         if run.rank == 0:
             print(f"{a.out}: epoch {run.epoch} of {run.plan.epochs}, {run.interacts} interactions, {run.elapsed:.1f} s")

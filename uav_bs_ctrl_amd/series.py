@@ -38,7 +38,7 @@ import numpy as np
 from . import run as R
 from .run import RunDirectoryError
 
-MODEL_KEYS = ("o", "c", "agent", "hidden_size", "n_layers", "n_heads", "msg_size", "key_size", "n_rounds", "dueling", "noisy")
+MODEL_KEYS = ("o", "c", "agent", "hidden_size", "n_layers", "n_heads", "msg_size", "key_size", "n_rounds", "dueling", "noisy", "quantiles")
 SUMMARY, SUMMARY_T, FIGURE = "test_summary.csv", "test_summary_t.csv", "test_summary.png"
 INFO_KEYS = ("EpRet", "EpLen", "AvgGlobalUtility", "TotalThroughput", "FairIdx", "ProbCollision")       # graphs.INFO_KEYS, without torch
 
@@ -138,6 +138,13 @@ def describe(run_dir: str, device="cuda") -> RunDescription:
         # and the evaluation - like every evaluation - uses the means
         try:
             ns.noisy = R._noisy(ours["noisy"])
+        except ValueError as e:
+            raise RunDirectoryError(f"{run_dir}: config.json is unreadable: {e}") from e
+    if ours is not None and ours.get("quantiles") is not None:
+        # the run trained the quantile-regression Q head (``Run.create(quantiles=K)``): the learner builds it, the checkpoint's
+        # [n_actions * K, H] head loads into it, and the evaluation acts on the quantile means
+        try:
+            ns.quantiles = R._quantiles(ours["quantiles"])
         except ValueError as e:
             raise RunDirectoryError(f"{run_dir}: config.json is unreadable: {e}") from e
     if exp == "exp1":
